@@ -7,10 +7,14 @@ classify -> K3 Gen+Disc+decision tensors -> K5 per-container moves
 (torchrun, or `--gpus N` starting N ranks itself); every rank processes its own batch of independent windows (weak
 scaling, no data-path collective); timing is max over ranks.
 
-Prints ONE JSON line (rank 0).  The roofline object is for the dominant kernel
-(K2, fp32 MFMA-bound); its kernel time is measured live with HIP events on the
-stream the kernels run on.  cpu_baseline times the numpy oracle (a CPU port of
-the reference math) on a bounded sample, rank 0 at N=1 only.
+Prints ONE JSON line (rank 0).  A plain run of the default config sets up,
+warms up, times --steps steps and prints the headline fields (value,
+ms_per_step, ...); --dump-outputs DIR also writes the last timed step's output
+arrays.  With --full the line carries the rest: the roofline object for the
+dominant kernel (K2, fp32 MFMA-bound), its kernel time measured live with HIP
+events on the stream the kernels run on in a pass after the timed steps, and
+cpu_baseline, which times the numpy oracle (a CPU port of the reference math)
+on a bounded sample, rank 0 at N=1 only.
 """
 import argparse
 import ctypes
@@ -101,6 +105,29 @@ def loaded_isa_hash(name, H, targs=None):
         return None
 
 
+DUMP_MAX_WINDOWS = 16384   # 454 values per window at H = 50: 30 MB of float32, under the 64 MB a dump may take
+
+
+def dump_outputs(folder, arrays, max_rows=DUMP_MAX_WINDOWS):
+    """--dump-outputs: every array of `arrays` (device tensors, first dimension
+    = the window) as folder/<name>.npy in float32 (the int32 decisions and
+    flags are small integers, exact in float32).  More than max_rows windows:
+    the same sorted sample of max_rows of them for every array, drawn with a
+    fixed seed, so two builds run with the same arguments write the same
+    windows."""
+    os.makedirs(folder, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None and not k.startswith("_")}
+    n = next(iter(arrays.values())).shape[0]
+    rows = None
+    if n > max_rows:
+        rows = np.sort(np.random.Generator(np.random.PCG64(2024)).choice(n, size=max_rows, replace=False))
+        rows = torch.as_tensor(rows, device=next(iter(arrays.values())).device)
+    for name, t in arrays.items():
+        a = (t if rows is None else t.index_select(0, rows)).detach().cpu().numpy()
+        np.save(os.path.join(folder, f"{name}.npy"), a.astype(np.float32))
+    log(f"wrote {len(arrays)} arrays ({n if rows is None else max_rows} of {n} windows) to {folder}")
+
+
 def launch_ranks(n, argv=None):
     """`python bench.py --gpus N` without a torchrun environment: start N ranks,
     one process per GPU, as a CHILD `torch.distributed.run` (the driver's own
@@ -127,6 +154,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--hosts", type=int, default=50)
     ap.add_argument("--batch", type=int, default=65536, help="windows per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: after the timed steps also take the per-stage HIP-event pass (kernel_ms, kernel "
+                         "rates, roofline and traffic fields) and time the CPU baseline; without it the run sets "
+                         "up, warms up, times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: after the timed steps write what the last one computed (the forward's output arrays "
+                         "and K5's moves, a fixed seeded sample of the windows) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-gan", action="store_true", help="tune config: Transformer tuning step only")
@@ -150,6 +184,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs is not None and args.config != "c2":
+        ap.error("--dump-outputs is for the default config (c2)")
+    if args.config == "c2" and args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
     global _GPUS_REQUESTED
@@ -213,19 +251,42 @@ def main():
     torch.cuda.synchronize()
     # the timed loop: events at its ends only (barrier + sync on both sides)
     elapsed = _timed(world, device, step, args.steps)
-    # per-stage HIP events in a separate pass right after (same inputs, same
-    # process): kernel times and the roofline's launch duration
-    n_prof = min(args.steps, 40)
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(NK + 1)] for _ in range(n_prof)]
-    for i in range(n_prof):
-        step(evs[i])
-    torch.cuda.synchronize()
-    k_ms = np.array([[e[k].elapsed_time(e[k + 1]) for k in range(NK)] for e in evs])  # [steps, NK]
-    k_mean = k_ms.mean(axis=0)
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step left in the caller's arrays (before any further pass)
+        dump_outputs(args.dump_outputs, {**out, "moves": mv_out[0], "hosts_from": mv_out[1]})
+    if args.full:
+        # per-stage HIP events in a separate pass right after (same inputs, same
+        # process): kernel times and the roofline's launch duration
+        n_prof = min(args.steps, 40)
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(NK + 1)] for _ in range(n_prof)]
+        for i in range(n_prof):
+            step(evs[i])
+        torch.cuda.synchronize()
+        k_ms = np.array([[e[k].elapsed_time(e[k + 1]) for k in range(NK)] for e in evs])  # [steps, NK]
+        k_mean = k_ms.mean(axis=0)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         hw = B * world * H * args.steps / elapsed
+        res = {
+            "metric": "host-windows/sec (detect+diagnose+generate)",
+            "value": hw,
+            "unit": "host-windows/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "fp32",
+            "data": "synthetic (SURVEY §8d C2 distribution; seeded random-init weights of the H=50 architecture)",
+            "config": {"workload": f"C2: PreGAN+ batched inference, {H} hosts x W=3 x 3 resources, "
+                                   f"{B} windows per GPU, fp32",
+                       "hosts": H, "windows_per_gpu": B, "parallelism": f"dp{world} (independent windows)"},
+            "cpu_baseline": None,
+        }
+    if rank == 0 and args.full:
         k2_s = k_mean[1] * 1e-3
         # executed work: the MFMAs K2 issues (ISA count); the reference formulation's
         # flops are reported beside it (the layer-0 folds issue 0.67x of them)
@@ -246,22 +307,7 @@ def main():
         ktargs = {"encoder": [H, esplit], "gan": [H, 16 if B >= 65536 else 4] if gsplit else None}
         k_traffic = {k: load_traffic(H, B, v, targs=ktargs.get(k)) for k, v in kn.items()}
         path_bytes = R.path_bytes_per_window(H) * B
-        res = {
-            "metric": "host-windows/sec (detect+diagnose+generate)",
-            "value": hw,
-            "unit": "host-windows/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (SURVEY §8d C2 distribution; seeded random-init weights of the H=50 architecture)",
-            "config": {"workload": f"C2: PreGAN+ batched inference, {H} hosts x W=3 x 3 resources, "
-                                   f"{B} windows per GPU, fp32",
-                       "hosts": H, "windows_per_gpu": B, "parallelism": f"dp{world} (independent windows)"},
+        res.update({
             "kernel_ms": {"gat_agg": k_mean[0], "encoder": k_mean[1], "decoder": k_mean[2], "gan": k_mean[3],
                           "moves": k_mean[4]},
             "kernel_tflops": {
@@ -308,12 +354,10 @@ def main():
                 "traffic_ratio": (None if None in k_traffic.values() else sum(k_traffic.values()) / path_bytes),
                 "traffic_by_kernel": k_traffic,
             },
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             log("timing CPU baseline ...")
             res["cpu_baseline"] = cpu_baseline(weights, x, s)
-        else:
-            res["cpu_baseline"] = None
     # sub-records (every rank takes part; rank 0 reports them in the line)
     # The headline never waits on a sub-record: an exception in one is recorded
     # in its place, and a sub-record still running after SUBRECORD_DEADLINE_S

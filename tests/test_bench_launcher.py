@@ -114,6 +114,34 @@ def test_subrecord_deadline_emits_the_line_and_ends_the_process():
     assert "not reached" not in p.stdout
 
 
+def test_dump_outputs_writes_the_same_float32_sample(tmp_path):
+    """bench.dump_outputs: every array as <name>.npy in float32; more windows
+    than the limit -> the same sorted seeded sample of rows for every array and
+    every call; None entries and private keys are left out."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1000
+    arrays = {"logits": torch.arange(n * 6, dtype=torch.float32).reshape(n, 3, 2),
+              "keep": torch.arange(n, dtype=torch.int32), "latent": None, "_buf": torch.zeros(4)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, max_rows=64)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, max_rows=64)
+    assert sorted(os.listdir(tmp_path / "a")) == ["keep.npy", "logits.npy"]
+    keep, logits = np.load(tmp_path / "a" / "keep.npy"), np.load(tmp_path / "a" / "logits.npy")
+    assert keep.dtype == logits.dtype == np.float32 and keep.shape == (64,) and logits.shape == (64, 3, 2)
+    assert np.all(np.diff(keep) > 0) and np.array_equal(logits[:, 0, 0], keep * 6)   # same rows, in order
+    assert np.array_equal(keep, np.load(tmp_path / "b" / "keep.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), arrays, max_rows=n)                       # all of them
+    assert np.array_equal(np.load(tmp_path / "c" / "keep.npy"), np.arange(n, dtype=np.float32))
+    assert 454 * 4 * bench.DUMP_MAX_WINDOWS <= 64 * 2 ** 20                            # C2 at H = 50
+
+
+def test_dump_outputs_is_for_the_default_config():
+    p = _run(["--config", "ranks", "--dump-outputs", "x"])
+    assert p.returncode == 2 and "--dump-outputs" in p.stderr
+
+
 def test_subrecord_deadline_returns_the_value_in_time():
     sys.path.insert(0, ROOT)
     import bench

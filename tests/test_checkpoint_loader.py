@@ -20,7 +20,7 @@ REF = "/root/reference/recovery/PreGANSrc"
 def test_loader_restores_training_state(folder, encoder, packaged):
     w, extra = W.load_reference_checkpoints(os.path.join(REF, folder), "simulator", 16, encoder=encoder,
                                             with_state=True)
-    pw, pe = W.load_npz(os.path.join("preganplus_amd", "data", packaged))
+    pw, pe = W.load_npz(os.path.join(os.path.dirname(os.path.abspath(W.__file__)), "data", packaged))
     opt = [k for k in pe if k.startswith("opt/")]
     assert opt and all(np.array_equal(extra[k], pe[k]) for k in opt)
     assert int(extra["meta/gen/epoch"]) == int(pe["meta/gen/epoch"]) == 199

@@ -13,7 +13,7 @@ run() {  # name, args...
   echo "[$n] rc=$rc $(cut -c1-160 "$OUT/$n.json")"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/$n.err"; exit $rc; fi
 }
-run c2
+run c2 --full
 run fleet --config fleet
 run tune50 --config tune
 run tune16 --config tune --hosts 16

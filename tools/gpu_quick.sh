@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest $TESTS -x -q -p no:cacheprovider --timeout 120 --timeout-method thread >"$OUT/tests.log" 2>&1 || { tail -30 "$OUT/tests.log"; exit 1; }
 tail -2 "$OUT/tests.log"
-timeout -k 10 300 python bench.py --no-cpu-baseline >"$OUT/bench_c2.json" 2>"$OUT/bench_c2.err" || { tail "$OUT/bench_c2.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline >"$OUT/bench_c2.json" 2>"$OUT/bench_c2.err" || { tail "$OUT/bench_c2.err"; exit 1; }
 cat "$OUT/bench_c2.json"
 timeout -k 10 300 python bench.py --config fleet --steps 20 --warmup 3 >"$OUT/bench_fleet.json" 2>"$OUT/bench_fleet.err" || { tail "$OUT/bench_fleet.err"; exit 1; }
 cat "$OUT/bench_fleet.json"

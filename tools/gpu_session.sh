@@ -33,7 +33,7 @@ for st in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" >"$OUT/smoke.log" 2>&1
       ok_or_stop $? smoke; tail -3 "$OUT/smoke.log";;
     bench)
-      timeout -k 10 600 python bench.py >"$OUT/bench.json" 2>"$OUT/bench.err"
+      timeout -k 10 600 python bench.py --full >"$OUT/bench.json" 2>"$OUT/bench.err"
       ok_or_stop $? bench; cat "$OUT/bench.json";;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \

@@ -12,10 +12,10 @@ ARGS=${*:-}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 300 python3 bench.py $ARGS >"$OUT/bench.json" 2>"$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python3 bench.py --full $ARGS >"$OUT/bench.json" 2>"$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-  -- python3 "$ROOT/bench.py" $ARGS >"$OUT/trace_bench.json" 2>"$OUT/trace.err" || { tail "$OUT/trace.err"; exit 1; }
+  -- python3 "$ROOT/bench.py" --full $ARGS >"$OUT/trace_bench.json" 2>"$OUT/trace.err" || { tail "$OUT/trace.err"; exit 1; }
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" \
     "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
