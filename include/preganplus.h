@@ -187,7 +187,9 @@ int pgp_schedule_onehot(int n_hosts, int batch, const unsigned char* idx, float*
  * (argmax of each host's softmax, :110-111), embedding + get_classes over the
  * K = 3 prototypes (:119-120), Gen_16/Disc_16 (recover_decision, :74-77).
  * ---------------------------------------------------------------------- */
-/* A PreGAN model for H hosts (H = 16 only: the reference defines FPE_16 alone). */
+/* A PreGAN model for H hosts (H = 16 or 50: the reference defines FPE_16 alone;
+ * H = 50 is that same architecture at 50 hosts; any other H returns
+ * PGP_ERR_UNSUPPORTED). */
 int pgp_create_fpe(int n_hosts, pgp_model** out);
 /* Doubles pgp_load_weights expects for an FPE model, row-major in this order:
  *   FPE: gru.weight_ih_l0 [9,3H], gru.weight_hh_l0 [9,3], gru.bias_ih_l0 [9],
@@ -300,6 +302,31 @@ int pgp_tune_reserve_cus(int n);
  * attention backward layer 0] in ms.  Off by default (not graph-capturable). */
 int pgp_tune_timing(int on);
 int pgp_tune_fused_ms(float* ms6);
+/* Which launch form a step takes (read-only: launches nothing, keeps no state;
+ * the answers follow the current device's CU count and pgp_tune_reserve_cus).
+ * pgp_tune_plan_info: for pgp_tune_forward(fwd_batch) followed by
+ * pgp_tune_backward_prefix(fwd_batch, batch) (batch == fwd_batch:
+ * pgp_tune_backward), writes the first min(cap, 11) of
+ *   [0]  1 if the backward forks side work onto the second stream (0: every
+ *        launch on the caller's stream, the weight gradients of the tail merged
+ *        into one launch); as the library's own side stream gives it: a
+ *        pgp_tune_set_side_stream equal to the call's stream forces 0
+ *   [1]  the same for the forward (the decoder weight packing)
+ *   [2]  workgroups of a fused encoder backward launch
+ *   [3]  16-pair units carried by its longest wave
+ *   [4]  workgroups of a fused encoder forward launch
+ *   [5]  units of its longest wave
+ *   [6]  workgroups of the row-block linear launches
+ *   [7]  workgroups of a weight-gradient (dW) launch
+ *   [8]  32-row blocks the busiest of them contracts
+ *   [9]  split-K parts of the forward's decoder GEMM
+ *   [10] window parts of the backward's decoder weight gradient
+ * into out and returns 11, or a negative PGP_ERR_*.
+ * pgp_gan_plan_info: the k-slices per 16-environment block of pgp_gan_forward /
+ * pgp_gan_disc_backward / pgp_gan_gen_backward at that batch (1: the unsplit
+ * form), or a negative PGP_ERR_*. */
+int pgp_tune_plan_info(int n_hosts, int fwd_batch, int batch, int* out, int cap);
+int pgp_gan_plan_info(int n_hosts, int batch);
 /* custom_loss / triplet_loss bookkeeping of ONE window (train.py:13-40,
  * replaces the host loop between `model(...)` and `loss.backward()` in
  * backprop, train.py:47-53), on the stream: reads the batch-1 forward's logits

@@ -469,6 +469,22 @@ int pgp_tune_timing(int on) {
   return PGP_OK;
 }
 
+int pgp_tune_plan_info(int n_hosts, int fwd_batch, int batch, int* out, int cap) {
+  if (!supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count");
+  if (!out || cap < 0 || batch < 1 || batch > fwd_batch) return fail(PGP_ERR_ARG, "bad tune_plan_info arguments");
+  int v[kTunePlanInfo];
+  if (!tune_plan_info(n_hosts, fwd_batch, batch, v)) return fail(PGP_ERR_ARG, "tune_plan_info plan");
+  for (int i = 0; i < kTunePlanInfo && i < cap; ++i) out[i] = v[i];
+  return kTunePlanInfo;
+}
+
+int pgp_gan_plan_info(int n_hosts, int batch) {
+  if (!supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count");
+  if (batch < 1) return fail(PGP_ERR_ARG, "batch >= 1");
+  const int s = gan_plan_slices(n_hosts, batch);
+  return s > 0 ? s : fail(PGP_ERR_UNSUPPORTED, "host count");
+}
+
 int pgp_tune_fused_ms(float* ms6) {
   if (!ms6) return fail(PGP_ERR_ARG, "NULL output");
   const hipError_t e = tune_fused_ms(ms6);

@@ -103,6 +103,7 @@ hipError_t launch_gan_split(const FwdArgs& a, hipStream_t st);
 struct AdamArgs;
 struct AdamFuse;
 long gan_workspace_floats(int H, int B);
+int gan_plan_slices(int H, int B);  // k-slices of the GAN step (pgp_gan_plan_info); 0: H not compiled
 hipError_t launch_adamw(const AdamArgs& a, hipStream_t st);
 // fused batch-1 GAN step (pgp_gan1.hip), H in {8, 16}
 bool gan1_supported(int H);

@@ -962,6 +962,19 @@ long gan_workspace_floats(int H, int B) {
   return 0;
 }
 
+// k-slices per 16-environment block of the GAN step at (H, B) (1: the unsplit
+// form); 0: H not compiled
+int gan_plan_slices(int H, int B) {
+  switch (H) {
+#define CASE(h) \
+  case h:       \
+    return gan_slices<h>(B);
+    PGP_FOR_EACH_H(CASE)
+#undef CASE
+  }
+  return 0;
+}
+
 hipError_t launch_gan_fwd(int H, int B, const float* emb, const float* sched, const float* Pg, const float* Pd,
                           float* ws, float* ns_out, float* probs, hipStream_t st, const float* logits,
                           const float* protos, float* emb_out) {

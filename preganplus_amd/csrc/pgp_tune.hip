@@ -1610,6 +1610,30 @@ bool tune_plan_prefix(int H, int B_fwd, int B, TunePlan* p) {
   return true;
 }
 
+// What a forward of B_fwd windows and a backward over its first B will launch
+// (pgp_tune_plan_info): read from the planner the launches themselves read,
+// nothing launched, nothing kept.
+bool tune_plan_info(int H, int B_fwd, int B, int (&out)[kTunePlanInfo]) {
+  TunePlan f, p;
+  if (!tune_plan(H, B_fwd, &f) || !tune_plan_prefix(H, B_fwd, B, &p)) return false;
+  out[0] = tune_side_active(p.M);  // Fork(st, p.M) of tune_bwd_h
+  out[1] = tune_side_active(f.M);  // ... of tune_fwd_h
+  int grid = 0;
+  tf_launch_shape(H, B, false, &grid, &out[3]);
+  out[2] = p.tf_grid;
+  if (grid != p.tf_grid) return false;  // launch_tf and the plan's slabs disagree
+  tf_launch_shape(H, B_fwd, true, &out[4], &out[5]);
+  out[6] = p.lin_grid;
+  out[7] = p.dw_grid;
+  // dw_block: the kDwRows-row chunks dealt over dw_grid workgroups, block bx
+  // taking chunks [nch bx / nbx, nch (bx + 1) / nbx): the most is the ceiling
+  const long nch = (p.M + kDwRows - 1) / kDwRows;
+  out[8] = (int)((nch + p.dw_grid - 1) / p.dw_grid);
+  out[9] = f.dec_s;  // the forward's decoder split-K (the backward has none)
+  out[10] = p.dec_dws;
+  return true;
+}
+
 hipError_t launch_tune_forward(const TunePlan& p, const float* windows, const float* P, float* ws, float* latent,
                                float* logits, float* protos, hipStream_t st, hipEvent_t post) {
   switch (p.H) {

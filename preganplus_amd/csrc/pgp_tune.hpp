@@ -61,6 +61,9 @@ struct TunePlan {
 bool tune_plan(int H, int B, TunePlan* p);
 // a backward over the first B windows of a forward of B_fwd (same workspace)
 bool tune_plan_prefix(int H, int B_fwd, int B, TunePlan* p);
+// the launch forms of that forward and backward, in pgp_tune_plan_info's order
+constexpr int kTunePlanInfo = 11;
+bool tune_plan_info(int H, int B_fwd, int B, int (&out)[kTunePlanInfo]);
 // live timing of the six fused encoder launches of a forward + backward
 // (pgp_tune_timing / pgp_tune_fused_ms)
 hipError_t tune_timing(bool on);

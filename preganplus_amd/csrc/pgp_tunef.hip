@@ -1362,6 +1362,13 @@ int tf_max_grid() { return device_cus(); }
 
 int tf_bwd_grid(int H, int B) { return tf_grid_for(((long)B * H + 15) / 16, kTfWaves); }
 
+void tf_launch_shape(int H, int B, bool forward, int* grid, int* units) {
+  const long nu = ((long)B * H + 15) / 16;
+  const int waves = forward ? kTfFwdWaves : kTfWaves;
+  *grid = tf_grid_for(nu, waves);
+  *units = (int)((nu + (long)waves * *grid - 1) / ((long)waves * *grid));  // unit_range: q + (r > 0)
+}
+
 void tf_reserve_cus(int n) { g_tf_reserve.store(n < 0 ? 0 : n, std::memory_order_relaxed); }
 
 #ifdef PGP_TF_STAMPS

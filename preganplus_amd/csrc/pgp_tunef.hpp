@@ -202,7 +202,9 @@ long tf_pack_items(int H);  // tf_pack_elem's index range (>= tf_frag_floats' fp
 long tf_slab_floats(int H, int kind);  // kind 2: ffn backward, 3: attention backward
 int tf_max_grid();                      // the most workgroups a fused launch uses (one per CU)
 int tf_bwd_grid(int H, int B);          // workgroups (= weight-gradient slabs) of a backward launch
-void tf_reserve_cus(int n);             // CUs the fused launches leave to other streams
+// workgroups of a forward / backward launch over B windows and the units of its longest wave
+void tf_launch_shape(int H, int B, bool forward, int* grid, int* units);
+void tf_reserve_cus(int n);           // CUs the fused launches leave to other streams
 // kind 0: pack fragments from P; 1: forward of a.layer; 2: ffn backward; 3: attention backward
 // stop != nullptr: the launch signals that event at its end (hipExtLaunchKernel)
 hipError_t launch_tf(int H, int kind, const TfArgs& a, hipStream_t st, hipEvent_t stop = nullptr);

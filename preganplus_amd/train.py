@@ -50,6 +50,43 @@ def default_lrs(H):
     return {"transformer": 1e-4, "gen": g, "disc": g}
 
 
+TUNE_PLAN_FIELDS = ("bwd_side", "fwd_side", "bwd_grid", "bwd_units", "fwd_grid", "fwd_units", "lin_grid",
+                    "dw_grid", "dw_blocks", "dec_s", "dec_dws")
+
+
+def tune_plan_info(H: int, batch: int, fwd_batch: int | None = None) -> dict:
+    """The launch form of ``tune_forward(fwd_batch)`` + ``tune_backward(batch)``
+    on the current device (``pgp_tune_plan_info``; launches nothing), by
+    TUNE_PLAN_FIELDS: side-stream form of the backward / forward (as the
+    library's own side stream gives it), workgroups and longest wave's units of
+    the fused backward / forward launches, linear and dW grids, 32-row blocks of
+    the busiest dW workgroup, the forward decoder's split-K parts, the decoder
+    weight gradient's window parts."""
+    L = _native.lib()
+    L.pgp_tune_plan_info.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.pgp_tune_plan_info.restype = ctypes.c_int
+    n = len(TUNE_PLAN_FIELDS)
+    out = (ctypes.c_int * n)()
+    rc = L.pgp_tune_plan_info(H, batch if fwd_batch is None else fwd_batch, batch, out, n)
+    if rc < 0:
+        _native.check(rc, "pgp_tune_plan_info")
+    if rc != n:
+        raise RuntimeError(f"pgp_tune_plan_info reports {rc} fields, this package knows {n}")
+    return dict(zip(TUNE_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def gan_plan_info(H: int, batch: int) -> int:
+    """k-slices per 16-environment block of the GAN step at that batch
+    (``pgp_gan_plan_info``; 1: the unsplit form)."""
+    L = _native.lib()
+    L.pgp_gan_plan_info.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.pgp_gan_plan_info.restype = ctypes.c_int
+    rc = L.pgp_gan_plan_info(H, batch)
+    if rc < 0:
+        _native.check(rc, "pgp_gan_plan_info")
+    return int(rc)
+
+
 class Trainer:
     """fp32 master weights in the natural blob order (prototypes excluded),
     gradients and AdamW moments, all on the device."""

@@ -258,12 +258,12 @@ def test_smaller_batch_after_larger_is_unchanged(H):
         assert np.array_equal(u, v)
 
 
-@pytest.mark.parametrize("H,B", [(8, 3), (16, 37), (50, 21), (64, 5), (16, 300)])
-def test_batched_gan_step_matches_autograd(H, B):
-    """GAN step over a ragged batch (pgp_gantrain.hip): new schedule and Disc
-    probabilities within fp32 tolerance of the fp64 forward; Disc gradients of
-    the summed BCE toward per-window targets, and Gen gradients of the summed
-    BCE toward [0,1] through the (unchanged) Disc == autograd (PreGANPlus.py:60-74)."""
+def gan_step_vs_autograd(H, B, check=close):
+    """The batched GAN step at (H, B) against fp64 autograd (the body of
+    test_batched_gan_step_matches_autograd; test_gpu_train_regimes.py runs it
+    at other slice counts).  ``check`` is close, or a wrapper that records the
+    error before calling it.  Returns the trainer, the step's inputs, and its
+    outputs ns, probs and G as numpy (for checks on the state the step leaves)."""
     from preganplus_amd import train as TR
     w = W.synth_weights(H, seed=4)
     rng = np.random.Generator(np.random.PCG64(21 + H + B))
@@ -283,13 +283,13 @@ def test_batched_gan_step_matches_autograd(H, B):
     e_t, s_t = torch.tensor(emb), torch.tensor(sched)
     ns_r = TO.gen_t(gw, e_t, s_t)
     p_r = TO.disc_t(dw, s_t, ns_r.detach())
-    close(ns, ns_r.detach().numpy(), rel=1e-4, abs_scale=1e-5, what="ns")
-    close(probs, p_r.detach().numpy(), rel=1e-4, abs_scale=1e-5, what="probs")
+    check(ns, ns_r.detach().numpy(), rel=1e-4, abs_scale=1e-5, what="ns")
+    check(probs, p_r.detach().numpy(), rel=1e-4, abs_scale=1e-5, what="probs")
     bce = torch.nn.functional.binary_cross_entropy
     torch.stack([bce(p_r[i], torch.tensor(target[i])) for i in range(B)]).sum().backward()
     for t in tr.tensors:
         if t["section"] == "disc":
-            close(g[t["offset"]:t["offset"] + t["n"]], dw[t["name"]].grad.numpy().reshape(-1), rel=1e-3,
+            check(g[t["offset"]:t["offset"] + t["n"]], dw[t["name"]].grad.numpy().reshape(-1), rel=1e-3,
                   abs_scale=1e-4, what="disc " + t["name"])
     for p in dw.values():
         p.grad = None
@@ -297,8 +297,18 @@ def test_batched_gan_step_matches_autograd(H, B):
     torch.stack([bce(p2[i], torch.tensor([0.0, 1.0], dtype=torch.float64)) for i in range(B)]).sum().backward()
     for t in tr.tensors:
         if t["section"] == "gen":
-            close(g[t["offset"]:t["offset"] + t["n"]], gw[t["name"]].grad.numpy().reshape(-1), rel=1e-3,
+            check(g[t["offset"]:t["offset"] + t["n"]], gw[t["name"]].grad.numpy().reshape(-1), rel=1e-3,
                   abs_scale=1e-4, what="gen " + t["name"])
+    return tr, emb, sched, target, ns, probs, g
+
+
+@pytest.mark.parametrize("H,B", [(8, 3), (16, 37), (50, 21), (64, 5), (16, 300)])
+def test_batched_gan_step_matches_autograd(H, B):
+    """GAN step over a ragged batch (pgp_gantrain.hip): new schedule and Disc
+    probabilities within fp32 tolerance of the fp64 forward; Disc gradients of
+    the summed BCE toward per-window targets, and Gen gradients of the summed
+    BCE toward [0,1] through the (unchanged) Disc == autograd (PreGANPlus.py:60-74)."""
+    gan_step_vs_autograd(H, B)
 
 
 def test_dp_tune_step_single_rank():

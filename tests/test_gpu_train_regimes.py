@@ -1,0 +1,342 @@
+"""GPU parity of the batched training steps in every launch regime the batch
+size selects ("training regimes"): the tuning step's one-stream
+("defer") and side-stream forms, fused waves carrying one, two or three
+16-pair units, the decoder weight gradient split over 1-4 window parts, capped
+weight-gradient grids, the prefix backward on another batch's regions, and the
+GAN step at every k-slice count.
+
+The reference is always fp64 autograd of the torch oracle
+(oracle/pregan_train_oracle.py), never a second run of the kernels, except
+where a test says bit-identical.  Every case first asserts the regime it is
+for through the library's plan query (``train.tune_plan_info`` /
+``train.gan_plan_info``), so a retuned threshold fails here instead of quietly
+moving the case into a regime another case already covers.  The regimes in the
+tables are those of a 256-CU device.
+
+Each comparison prints ``ratio <case> <tensor> <max error / tolerance>`` before
+it asserts (pytest -s shows them; DESIGN.md records them).
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import pregan_train_oracle as TO
+from preganplus_amd import _native
+from tests.test_gpu_train import _autograd, _batched_case, close, gan_step_vs_autograd
+
+pytestmark = pytest.mark.gpu
+SEED = 3
+GRAD = dict(rel=1e-3, abs_scale=1e-4)     # gradients (the project's tolerances, unchanged)
+ACT = dict(rel=1e-4, abs_scale=1e-5)      # activations
+REGROUP = dict(rel=1e-4, abs_scale=1e-5)  # two fp32 summation groupings of the same gradient
+
+
+def _checker(case):
+    """close(), printing the worst error / tolerance ratio first."""
+    def check(got, want, rel, abs_scale, what=""):
+        w = np.asarray(want, dtype=np.float64)
+        g = np.asarray(got, dtype=np.float64)
+        tol = rel * np.abs(w) + abs_scale * (np.abs(w).max() + 1e-30)
+        print(f"ratio {case} {what} {float((np.abs(g - w) / tol).max()):.4f}")
+        close(got, want, rel=rel, abs_scale=abs_scale, what=f"{case} {what}")
+    return check
+
+
+def _assert_plan(info, want, where):
+    got = {k: info[k] for k in want}
+    assert got == want, f"{where}: planned {got}, this case is for {want} (all: {info})"
+
+
+def _reference(H, F, B):
+    """fp64 oracle of the case _batched_case(H, F): forward of all F windows,
+    autograd of the summed losses of the first B; read-only arrays.  The one
+    shape several tests use is computed once and kept."""
+    return (_kept_reference if (H, F, B) == (50, 657, 657) else _compute_reference)(H, F, B)
+
+
+def _compute_reference(H, F, B):
+    w, x, y, mult, tgt = _batched_case(H, F, seed=SEED)
+    tw, lat, logits, protos = _autograd(w, x[:B], y[:B], mult[:B], tgt[:B])
+    if F > B:   # the appended (inference) windows: forward only
+        with torch.no_grad():
+            lat2 = TO.encode_t(tw, torch.tensor(x[B:]))
+            lg2, pr2 = TO.decode_t(tw, lat2)
+        lat = np.concatenate([lat, lat2.numpy()])
+        logits = np.concatenate([logits, lg2.numpy()])
+        protos = np.concatenate([protos, pr2.numpy()])
+    out = {"latent": lat, "logits": logits, "protos": protos}
+    out.update({"grad/" + k: v.grad.numpy().reshape(-1).copy() for k, v in tw.items() if v.grad is not None})
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+_kept_reference = functools.lru_cache(maxsize=None)(_compute_reference)
+
+
+class _Step:
+    """One trainer on the case _batched_case(H, F): forward over F windows,
+    backward over the first B."""
+
+    def __init__(self, H, F, B=None, g_fill=0.0, y_zero=False):
+        from preganplus_amd import train as TR
+        self.H, self.F, self.B = H, F, F if B is None else B
+        w, x, y, mult, tgt = _batched_case(H, F, seed=SEED)
+        B = self.B
+        self.tr = TR.Trainer(H, w, max_batch=F)
+        dev = self.tr.device
+        self.tr.G.fill_(g_fill)
+        self.x = torch.tensor(x, dtype=torch.float32, device=dev)
+        self.y = torch.tensor(np.zeros_like(y[:B]) if y_zero else y[:B], dtype=torch.int32, device=dev)
+        self.mult = torch.tensor(mult[:B], dtype=torch.float32, device=dev)
+        self.tgt = torch.tensor(tgt[:B], dtype=torch.float32, device=dev)
+        self.lat = torch.empty((F, 3 * H * H), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+
+    def run(self):
+        """Returns G as numpy; latent / logits / protos stay in self."""
+        tr = self.tr
+        self.logits, self.protos = tr.tune_forward(self.x, latent=self.lat)
+        tr.tune_backward(self.B, self.y, self.mult, self.tgt)
+        torch.cuda.current_stream(tr.device).synchronize()
+        return tr.G.cpu().numpy().copy()
+
+    def trainable(self):
+        return [t for t in self.tr.tensors if t["section"] == "transformer" and t["trainable"]]
+
+    def verify(self, g, case):
+        """Latent, logits and protos of all F windows and every trainable
+        transformer gradient against the fp64 oracle; the GAN sections of a
+        zero-filled G stay exactly zero."""
+        ref = _reference(self.H, self.F, self.B)
+        check = _checker(case)
+        check(self.lat.cpu().numpy(), ref["latent"], what="latent", **ACT)
+        check(self.logits.cpu().numpy(), ref["logits"], what="logits", **ACT)
+        check(self.protos.cpu().numpy(), ref["protos"], what="protos", **ACT)
+        for t in self.trainable():
+            check(g[t["offset"]:t["offset"] + t["n"]], ref["grad/" + t["name"]], what=t["name"], **GRAD)
+        assert np.all(g[self.tr.sec_end["transformer"]:] == 0)
+
+
+# (H, B): the plan fields the case is for, and B * H mod 16 (a partial last tile).
+# (At (50, 436) gat.attn_fc.weight sits at 0.61 of its tolerance, every other
+# gradient below 0.003: window 81 of that data has one GAT edge 1.8e-8 from the
+# leaky-ReLU kink, where fp32 and fp64 take different slopes; DESIGN.md,
+# "Training regimes".)
+TUNE_REGIMES = [
+    (8, 2049, dict(bwd_side=0, bwd_units=2, dec_dws=4), 8),
+    (16, 1025, dict(bwd_side=0, bwd_units=2, dec_dws=4), 0),
+    (32, 683, dict(bwd_side=1, dec_dws=2), 0),
+    (50, 328, dict(bwd_side=0, bwd_units=2, dec_dws=1), 0),
+    (50, 436, dict(bwd_side=0, fwd_side=0), 8),
+    (50, 437, dict(bwd_side=1, fwd_side=1), 10),
+    (50, 657, dict(bwd_side=1, fwd_side=1, fwd_units=2, bwd_units=3, dec_dws=2), 2),
+    (50, 737, dict(bwd_side=1, dec_dws=3), 2),
+    (64, 342, dict(bwd_side=1), 0),
+    (64, 513, dict(bwd_side=1, fwd_units=2), 0),
+]
+
+
+@pytest.mark.parametrize("H,B,regime,tail", TUNE_REGIMES, ids=[f"{h}-{b}" for h, b, _, _ in TUNE_REGIMES])
+def test_tuning_step_matches_autograd_in_regime(H, B, regime, tail):
+    """(a) The smallest batches that cross each launch rule of the tuning step:
+    latent, logits, protos and every trainable transformer gradient against
+    fp64 autograd; the GAN sections of G stay exactly zero."""
+    from preganplus_amd import train as TR
+    info = TR.tune_plan_info(H, B)
+    _assert_plan(info, regime, f"H={H} B={B}")
+    assert (B * H) % 16 == tail
+    if (H, B) == (32, 683):     # the first side-form batch at H = 32
+        assert TR.tune_plan_info(H, B - 1)["bwd_side"] == 0
+    if (H, B) == (50, 657):     # the dW grid is at its cap and its row blocks are dealt unevenly
+        assert info["dw_grid"] == TR.tune_plan_info(H, 4 * B)["dw_grid"]
+        assert info["dw_blocks"] * info["dw_grid"] > (B * 3 * H + 31) // 32 > (info["dw_blocks"] - 1) * info["dw_grid"]
+        assert info["dw_blocks"] > TR.tune_plan_info(H, 16)["dw_blocks"]
+    s = _Step(H, B)
+    s.verify(s.run(), f"tune({H},{B})")
+
+
+def _bind_side_stream():
+    L = _native.lib()
+    L.pgp_tune_set_side_stream.argtypes = [ctypes.c_void_p]
+    L.pgp_tune_set_side_stream.restype = ctypes.c_int
+    return L
+
+
+def test_side_form_agrees_with_one_stream_form():
+    """(b) (50, 657) on the library's side stream and, with the call's own
+    stream named as the side stream, all on that one stream: the defer form
+    with the decoder weight gradient in 2 parts, which no batch gets by
+    default.  Both against autograd, and against each other to fp32 summation
+    tolerance.  With another stream of the caller's as the side stream the
+    side form runs the same launches: bit-identical to the library's stream."""
+    from preganplus_amd import train as TR
+    H, B = 50, 657
+    _assert_plan(TR.tune_plan_info(H, B), dict(bwd_side=1, fwd_side=1, dec_dws=2), "side form")
+    s = _Step(H, B)
+    own = torch.cuda.Stream(device=s.tr.device)   # a non-null handle (NULL selects the library's stream)
+    L = _bind_side_stream()
+    with torch.cuda.stream(own):
+        g_side = s.run()
+        try:
+            _native.check(L.pgp_tune_set_side_stream(ctypes.c_void_p(own.cuda_stream)), "pgp_tune_set_side_stream")
+            s.tr.G.zero_()
+            g_one = s.run()
+        finally:
+            _native.check(L.pgp_tune_set_side_stream(None), "pgp_tune_set_side_stream")
+        s.verify(g_one, f"tune({H},{B}) one-stream")
+        s.tr.G.zero_()
+        g_side2 = s.run()
+        # a second stream of the caller's as the side stream (a data-parallel
+        # caller's form): the same launches, so the same bits
+        other = torch.cuda.Stream(device=s.tr.device)
+        try:
+            _native.check(L.pgp_tune_set_side_stream(ctypes.c_void_p(other.cuda_stream)),
+                          "pgp_tune_set_side_stream")
+            s.tr.G.zero_()
+            g_other = s.run()
+        finally:
+            _native.check(L.pgp_tune_set_side_stream(None), "pgp_tune_set_side_stream")
+        other.synchronize()
+    assert np.array_equal(g_side, g_side2)       # the override is gone
+    assert np.array_equal(g_side, g_other)
+    s.verify(g_side, f"tune({H},{B}) side")
+    check = _checker(f"tune({H},{B}) side vs one-stream")
+    for t in s.trainable():
+        sl = slice(t["offset"], t["offset"] + t["n"])
+        check(g_side[sl], g_one[sl], what=t["name"], **REGROUP)
+
+
+def test_side_form_is_deterministic():
+    """(c) Two identical steps in the side-stream form give bit-identical G
+    (fixed slabs reduced in a fixed order, whatever the two streams' timing)."""
+    from preganplus_amd import train as TR
+    H, B = 50, 657
+    _assert_plan(TR.tune_plan_info(H, B), dict(bwd_side=1, fwd_side=1), "side form")
+    s = _Step(H, B)
+    g1 = s.run()
+    g2 = s.run()
+    assert np.array_equal(g1, g2)
+
+
+PREFIX_REGIMES = [
+    (50, 500, 430, dict(fwd_side=1, bwd_side=0)),
+    (50, 700, 657, dict(fwd_side=1, bwd_side=1, bwd_units=3, dec_dws=2)),
+    (16, 1128, 1025, dict(fwd_side=0, bwd_side=0, bwd_units=2, dec_dws=4)),
+]
+
+
+@pytest.mark.parametrize("H,F,B,regime", PREFIX_REGIMES, ids=[f"{h}-{f}-{b}" for h, f, b, _ in PREFIX_REGIMES])
+def test_prefix_backward_matches_autograd_of_the_prefix(H, F, B, regime):
+    """(d) Forward over F windows, backward over the first B (regions laid out
+    by F's plan, launch geometry of B's): gradients against autograd of the
+    first B windows alone; latent, logits and protos of all F windows, the
+    appended ones included, against the oracle's forward."""
+    from preganplus_amd import train as TR
+    info = TR.tune_plan_info(H, B, fwd_batch=F)
+    _assert_plan(info, regime, f"H={H} fwd={F} bwd={B}")
+    alone = TR.tune_plan_info(H, B)
+    assert all(info[k] == alone[k] for k in ("bwd_side", "bwd_grid", "bwd_units", "lin_grid", "dw_grid", "dec_dws"))
+    s = _Step(H, F, B)
+    s.verify(s.run(), f"prefix({H},{F},{B})")
+
+
+WRITE_CASES = [(16, 37, 37), (50, 437, 437), (50, 500, 430)]
+
+
+@pytest.mark.parametrize("H,F,B", WRITE_CASES, ids=[f"{h}-{f}-{b}" for h, f, b in WRITE_CASES])
+def test_tune_backward_writes_every_trainable_entry(H, F, B):
+    """(e) include/preganplus.h: pgp_tune_backward[_prefix] WRITES the
+    transformer section, no zeroing needed.  From a NaN-filled G every
+    trainable entry comes out finite and bit-identical to the same step from a
+    zero-filled G; the positional encoding's entries and the gen / disc
+    sections are left as they were."""
+    g0 = _Step(H, F, B).run()
+    s = _Step(H, F, B, g_fill=float("nan"))
+    g = s.run()
+    tr = s.tr
+    for t in tr.tensors:
+        if t["section"] != "transformer":
+            continue
+        sl = slice(t["offset"], t["offset"] + t["n"])
+        if t["trainable"]:
+            assert np.isfinite(g[sl]).all(), f"{t['name']}: {np.isnan(g[sl]).sum()} of {t['n']} entries not written"
+            assert np.array_equal(g[sl], g0[sl]), t["name"]
+        else:
+            assert np.isnan(g[sl]).all(), t["name"]
+    assert np.isnan(g[tr.sec_end["transformer"]:]).all()
+
+
+@pytest.mark.parametrize("H,B", [(16, 37), (50, 437), (16, 1025)])
+def test_tune_backward_without_positive_labels_writes_zero_prototype_gradient(H, B):
+    """(e) A batch with no positive label gives the prototype decoder no loss:
+    its gradient is WRITTEN as exact zeros (one, and at (16, 1025) four, window
+    parts of the decoder weight gradient), not left as it was."""
+    s = _Step(H, B, g_fill=float("nan"), y_zero=True)
+    g = s.run()
+    for t in s.trainable():
+        sl = slice(t["offset"], t["offset"] + t["n"])
+        assert np.isfinite(g[sl]).all(), t["name"]
+        if t["name"].startswith("prototype_decoder."):
+            assert np.all(g[sl] == 0), t["name"]
+    anomaly = [t for t in s.trainable() if t["name"].startswith("anomaly_decoder.")]
+    assert anomaly and all(np.any(g[t["offset"]:t["offset"] + t["n"]] != 0) for t in anomaly)
+
+
+def _gan_case(H, B):
+    rng = np.random.Generator(np.random.PCG64(77 + H + B))
+    emb = np.where(rng.uniform(size=(B, H, 1)) < 0.3, rng.uniform(size=(B, H, 2)), 0.0).astype(np.float32)
+    sched = np.zeros((B, H, H), np.float32)
+    sched[np.arange(B)[:, None], np.arange(H)[None, :], rng.integers(0, H, size=(B, H))] = 1.0
+    lab = rng.uniform(size=B) < 0.5
+    return emb, sched, np.stack([1.0 - lab, lab], axis=1).astype(np.float32)
+
+
+@pytest.mark.parametrize("H,B", [(16, 37), (50, 21), (50, 1361)])
+def test_gan_backwards_write_their_sections(H, B):
+    """(e) pgp_gan_disc_backward / pgp_gan_gen_backward WRITE the disc / gen
+    sections (unsplit at H = 16, 16 slices, unsplit at H = 50): from a
+    NaN-filled G both come out finite and bit-identical to the step from a
+    zero-filled G, and the transformer section is untouched."""
+    from preganplus_amd import train as TR
+    from preganplus_amd import weights as W
+    w = W.synth_weights(H, seed=4)
+    emb, sched, target = _gan_case(H, B)
+    gs = []
+    for fill in (0.0, float("nan")):
+        tr = TR.Trainer(H, w, max_batch=B)
+        tr.G.fill_(fill)
+        tr.gan_forward(emb, sched)
+        tr.gan_disc_backward(target)
+        tr.gan_gen_backward(B)
+        torch.cuda.synchronize()
+        gs.append(tr.G.cpu().numpy().copy())
+    g0, g = gs
+    gan = slice(tr.sec_off["gen"], tr.sec_end["disc"])
+    assert np.isfinite(g[gan]).all(), f"{np.isnan(g[gan]).sum()} GAN gradient entries not written"
+    assert np.array_equal(g[gan], g0[gan])
+    assert np.any(g[tr.sec_off["gen"]:tr.sec_end["gen"]] != 0) and np.any(g[tr.sec_off["disc"]:] != 0)
+    assert np.isnan(g[:tr.sec_end["transformer"]]).all()
+
+
+GAN_REGIMES = [(32, 9, 8), (32, 600, 7), (50, 1, 16), (50, 273, 15), (50, 577, 7), (50, 1361, 1), (64, 577, 7)]
+
+
+@pytest.mark.parametrize("H,B,S", GAN_REGIMES, ids=[f"{h}-{b}-S{s}" for h, b, s in GAN_REGIMES])
+def test_gan_step_matches_autograd_at_slice_count(H, B, S):
+    """(f) The GAN step at S k-slices per block (the cap of 8 at H = 32, 16 on a
+    one-environment block, intermediate counts whose chunks divide unevenly,
+    the unsplit form at H >= 32): ns, probs, Disc and Gen gradients against
+    autograd.  The step then runs again on the same workspace: the same bits,
+    so the split form's per-block counters and partials were left clean."""
+    from preganplus_amd import train as TR
+    assert TR.gan_plan_info(H, B) == S
+    tr, emb, sched, target, ns, probs, g = gan_step_vs_autograd(H, B, check=_checker(f"gan({H},{B})"))
+    ns2, probs2 = tr.gan_forward(emb, sched)
+    assert np.array_equal(ns2.cpu().numpy(), ns) and np.array_equal(probs2.cpu().numpy(), probs)
+    tr.gan_disc_backward(target)
+    tr.gan_gen_backward(B)
+    assert np.array_equal(tr.G.cpu().numpy(), g)
