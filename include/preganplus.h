@@ -556,18 +556,21 @@ int pgp_online_steps(const pgp_online* h, double* steps, int n);
 int pgp_online_gan_step(pgp_online* h, void* stream);
 
 /* ---------------------------------------------------------------------------
- * Offline training of PreGAN's FPE_16 (PreGAN.py:26-27, 39-49: a new FPE is
- * trained when no checkpoint exists, train.py:42-57).  P / G: the FPE's
- * parameters, natural fp32 blob in state_dict order (pgp_fpe_param_len(16) =
- * 11401 floats).
+ * Offline training of PreGAN's FPE for H hosts (PreGAN.py:26-27, 39-49: a new
+ * FPE is trained when no checkpoint exists, train.py:42-57).  H = 16 or 50:
+ * the reference defines FPE_16 alone; H = 50 is that same architecture at 50
+ * hosts; any other H returns PGP_ERR_UNSUPPORTED (pgp_fpe_param_len: 0).
+ * P / G: the FPE's parameters, natural fp32 blob in state_dict order
+ * (pgp_fpe_param_len(H) floats: 11401 for 16 hosts, 93137 for 50).
  * pgp_fpe_train_step: one sequential batch-1 step of backprop: FPE forward of
- *   window [3,48] with GRU state h0 [3] (the reference's torch.randn draw,
+ *   window [3,3H] with GRU state h0 [3] (the reference's torch.randn draw,
  *   models.py:70), custom_loss / triplet_loss bookkeeping on state [2K+3]
  *   fp64 (prototypes [K][2], factor, num_zero, num_ones; as pgp_tune_targets),
- *   loss [2] fp64 = (aloss, tloss), and the gradient WRITTEN into G.  The
- *   AdamW step that follows is pgp_adamw / pgp_adamw_table over P, G.
+ *   y / cls [H], loss [2] fp64 = (aloss, tloss), and the gradient WRITTEN
+ *   into G (every element; the same bits from run to run).  The AdamW step
+ *   that follows is pgp_adamw / pgp_adamw_table over P, G.
  * pgp_fpe_forward_many: n independent forwards (accuracy(), train.py:94-109):
- *   windows [n,3,48], h0 [n,3] -> probs / protos [n,16,2] fp64. */
+ *   windows [n,3,3H], h0 [n,3] -> probs / protos [n,H,2] fp64. */
 size_t pgp_fpe_param_len(int n_hosts);
 int pgp_fpe_train_step(int n_hosts, int n_protos, const float* window, const float* h0, const int* y, const int* cls,
                        const float* P, float* G, double* state, double update_min, double decay, double* loss,

@@ -1,26 +1,45 @@
 // pgp_fpetrain.hip — offline training of PreGAN's FPE_16 encoder
 // (PreGAN.py:26-27, 39-49: a new FPE is trained for num_epochs when no
-// checkpoint exists; train.py:42-57 backprop, sequential batch-1 steps).
+// checkpoint exists; train.py:42-57 backprop, sequential batch-1 steps),
+// compiled for H = 16 hosts and for H = 50 (FPE_16's architecture with its
+// constants set for 50 hosts, as K4's 50-host forward: the reference's FPE_50
+// class cannot run).
 //
-// fpe_step_kernel: ONE window per workgroup (256 threads), the whole step:
+// fpe_step_kernel<H, TRAIN>: ONE window per workgroup (256 threads), the whole step:
 //   forward of FPE_16 (models.py:65-115) from the natural fp32 master P —
-//     GRU(48 -> 3) over the 3 window rows from the given h0 (the reference
+//     GRU(3H -> 3) over the 3 window rows from the given h0 (the reference
 //     draws it with torch.randn inside encode, models.py:70; the host draws it
-//     the same way and passes it in), GAT on each row (16 nodes, graph-wise
-//     edge softmax, node mean), concat, MultiheadAttention(19, 1 head) over
-//     the 3 rows, encoder Linear(57 -> 160) (LeakyReLU(True) = identity),
+//     the same way and passes it in), GAT on each row (H nodes, graph-wise
+//     edge softmax, node mean), concat, MultiheadAttention(H + 3, 1 head) over
+//     the 3 rows, encoder Linear(3(H + 3) -> 10H) (LeakyReLU(True) = identity),
 //     per host Softmax(Linear(10, 2)) and Sigmoid(Linear(10, 2));
 //   custom_loss / triplet_loss bookkeeping of the window on the device state
 //     (pgp_tunetargets.hpp, fp64, the reference's order; the anomaly decoder
 //     ends in a Softmax, so CrossEntropyLoss sees probabilities);
 //   the backward of aloss + tloss into G (every element written).
-// With train = 0 the kernel stops after the forward and writes the window's
-// probabilities / prototypes (fp64), one workgroup per window: accuracy()'s
-// forwards (train.py:94-109) after an epoch.
-// The model is tiny (11,401 parameters, ~10^5 MACs per window): every phase is
-// a few hundred independent dot products over LDS-resident activations, so
+// The TRAIN = false instantiation stops after the forward and writes the
+// window's probabilities / prototypes (fp64), one workgroup per window:
+// accuracy()'s forwards (train.py:94-109) after an epoch.  It holds none of
+// the backward's LDS.
+// The model is tiny (11,401 parameters at 16 hosts, 93,137 at 50): every phase
+// is a few hundred independent dot products over LDS-resident activations, so
 // one workgroup per step is latency-bound by construction; the step count
 // (windows x epochs) is what the offline training costs.
+//
+// H = 16 keeps one thread per item and its summation orders.  At H = 50 the
+// `if constexpr (H > 16)` forms replace what does not scale:
+//   - the H^2 edge arrays (softmax, its gradient) and the dz array are not
+//     kept: an edge weight is exp(lrelu(s_i + t_j) - max) / sum and is
+//     recomputed where the backward needs it, d a_ij does not depend on j, and
+//     dz is consumed as it is produced.  LDS stays static (z is the one large
+//     array, 30.6 KB);
+//   - reductions over the H nodes of a row run on one wave per row, and long
+//     dot products (the GRU input gates, the encoder Linear, the attn_fc / fc
+//     gradients) on 16 lanes per output with lanes striding the terms, both
+//     reduced by a shuffle butterfly: a fixed order, the same bits every run;
+//   - every one-thread-per-item phase with more than 256 items is a strided
+//     loop (for_items picks the form from the item count); the others are
+//     covered by the static_asserts in the kernel.
 #include <hip/hip_runtime.h>
 
 #include "pgp_device.hpp"
@@ -30,35 +49,75 @@ namespace pgp {
 namespace {
 
 // natural parameter blob (state_dict order, weights.fpe_shapes)
+template <int H_>
 struct FP {
-  static constexpr int H = 16, F = 48, W = 3, G3 = 9, E = 19, L = 10, D = 16, Q = 3 * E, NL = H * L, NF = W * E;
+  static constexpr int H = H_, F = 3 * H, W = 3, G3 = 9, E = H + 3, L = 10, D = H, Q = 3 * E, NL = H * L, NF = W * E;
   static constexpr int IH = 0, HH = IH + G3 * F, BIH = HH + G3 * 3, BHH = BIH + G3, FC = BHH + G3, ATT = FC + D * 3,
                        IN = ATT + 2 * D, INB = IN + Q * E, OUT = INB + Q, OUTB = OUT + E * E, ENC = OUTB + E,
                        ENCB = ENC + NL * NF, AN = ENCB + NL, ANB = AN + 2 * L, PR = ANB + 2, PRB = PR + 2 * L,
                        SIZE = PRB + 2;
 };
-static_assert(FP::SIZE == 11401, "FPE_16 parameter count");
+static_assert(FP<16>::SIZE == 11401, "FPE_16 parameter count");
+static_assert(FP<50>::SIZE == 93137, "FPE_16 at 50 hosts: parameter count");
 
 constexpr int kFT = 256;
+constexpr int kSub = 16;  // lanes per output of a long dot product (H > 16)
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
-__global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const float* __restrict__ wins,
+// Butterfly reductions (H > 16): every lane of the wave calls them and gets the
+// result; the order of the additions is fixed, so a step repeats bit for bit.
+__device__ __forceinline__ float sub_sum(float v) {  // over the kSub lanes of a thread's group
+#pragma unroll
+  for (int m = kSub / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, kSub);
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// N items over the workgroup: one thread per item where they fit (every such phase at 16
+// hosts), a strided loop where they do not
+template <int N, class F>
+__device__ __forceinline__ void for_items(int t, F f) {
+  if constexpr (N <= kFT) {
+    if (t < N) f(t);
+  } else {
+    for (int k = t; k < N; k += kFT) f(k);
+  }
+}
+
+template <int H_, bool TRAIN>
+__global__ __launch_bounds__(kFT) void fpe_step_kernel(int K, const float* __restrict__ wins,
                                                        const float* __restrict__ h0s, const int* __restrict__ ys,
                                                        const int* __restrict__ clss, const float* __restrict__ P,
                                                        float* __restrict__ G, double* __restrict__ state,
                                                        double update_min, double decay, double* __restrict__ loss,
                                                        double* __restrict__ probs_out, double* __restrict__ protos_out) {
-  using C = FP;
+  using C = FP<H_>;
   constexpr int H = C::H, W = C::W, E = C::E, D = C::D, L = C::L;
+  constexpr bool kWide = H > 16;         // the 50-host forms
+  constexpr int HA = kWide ? 1 : H;      // the H^2 edge arrays and dz are kept at 16 hosts only
+  static_assert(H <= 64 && W <= kFT / 64, "one 64-lane wave (gfx950) reduces the H nodes of a row");
+  static_assert(W * H <= kFT && W * D + W * 3 <= kFT && 4 * H <= kFT, "one thread per item");
+  static_assert(64 + W * E <= kFT && C::Q <= kFT && C::NF <= kFT && 3 * D <= kFT, "one thread per item");
   const int t = threadIdx.x;
   const int b = blockIdx.x;  // window (forward-only launches: one per window; training: 0)
+  const int wv = t >> 6, ln = t & 63;    // wave and lane (kWide: wave w reduces row w)
+  const int sg = t / kSub, sl = t % kSub;  // group of kSub lanes and lane in it (kWide: one output per group)
   __shared__ float x[W][C::F];
   __shared__ float hs[W + 1][3];           // GRU states h_0 .. h_3
   __shared__ float gi[W][9], gh[W][9], gr[W][3], gz[W][3], gn[W][3];
   __shared__ float z[W][H][D + 1];         // GAT fc outputs
   __shared__ float sv[W][H], tv[W][H];     // attention halves a1.z_i, a2.z_j
-  __shared__ float al[W][H][H + 1];        // edge softmax
+  __shared__ float al[W][HA][HA + 1];      // edge softmax
   __shared__ float red[W][H];
   __shared__ float mx[W], sm[W];
   __shared__ float c[W][E];                // concat
@@ -68,7 +127,7 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
   __shared__ float fl[C::NF];              // out_proj output, flattened
   __shared__ float lat[C::NL];
   __shared__ float pr[H][2], an[H][2];     // prototypes (sigmoid), anomaly probs
-  // backward
+  // backward (no use in the TRAIN = false instantiation: not allocated there)
   __shared__ float mult[H], tgt[H][2];
   __shared__ double lsum[2];
   __shared__ float dan[H][2], dpr[H][2];
@@ -79,9 +138,10 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
   __shared__ float dc[W][E];
   __shared__ float dh[W + 1][3];
   __shared__ float dgi[W][9], dgh[W][9];
-  __shared__ float dz[W][H][D + 1];
-  __shared__ float dal[W][H][H + 1];
+  __shared__ float dz[W][HA][HA + 1];
+  __shared__ float dal[W][HA][HA + 1];
   __shared__ float dsv[W][H], dtv[W][H];
+  __shared__ float dav[W][H], ss[W];       // kWide: d a_ij (the same for every j), sum over edges of a . da
 
   const float* win = wins + (long)b * W * C::F;
   for (int k = t; k < W * C::F; k += kFT) x[k / C::F][k % C::F] = win[k];
@@ -89,11 +149,24 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
   __syncthreads();
 
   // ---- GRU (torch gate order r, z, n), one row at a time ----
+  if constexpr (kWide) {  // the input gates of all rows ahead of the recurrence, kSub lanes per gate
+    for (int base = 0; base < W * 9; base += kFT / kSub) {
+      const int o = base + sg, w = o / 9, g = o % 9;
+      float a = 0.f;
+      if (o < W * 9)
+        for (int k = sl; k < C::F; k += kSub) a = fmaf(P[C::IH + g * C::F + k], x[w][k], a);
+      a = sub_sum(a);
+      if (o < W * 9 && sl == 0) gi[w][g] = P[C::BIH + g] + a;
+    }
+    __syncthreads();
+  }
   for (int w = 0; w < W; ++w) {
     if (t < 9) {
-      float a = P[C::BIH + t];
-      for (int k = 0; k < C::F; ++k) a = fmaf(P[C::IH + t * C::F + k], x[w][k], a);
-      gi[w][t] = a;
+      if constexpr (!kWide) {
+        float a = P[C::BIH + t];
+        for (int k = 0; k < C::F; ++k) a = fmaf(P[C::IH + t * C::F + k], x[w][k], a);
+        gi[w][t] = a;
+      }
     } else if (t < 18) {
       const int o = t - 9;
       float a = P[C::BHH + o];
@@ -120,63 +193,91 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
     z[w][i][d] = fc[0] * x[w][3 * i] + fc[1] * x[w][3 * i + 1] + fc[2] * x[w][3 * i + 2];
   }
   __syncthreads();
-  if (t < 2 * W * H) {
-    const int half = t / (W * H), w = (t / H) % W, i = t % H;
+  for_items<2 * W * H>(t, [&](int k) {
+    const int half = k / (W * H), w = (k / H) % W, i = k % H;
     const float* a = P + C::ATT + half * D;
     float s = 0.f;
     for (int d = 0; d < D; ++d) s = fmaf(a[d], z[w][i][d], s);
     (half ? tv : sv)[w][i] = s;
-  }
+  });
   __syncthreads();
-  for (int k = t; k < W * H * H; k += kFT) {  // e_ij = lrelu(a1.z_i + a2.z_j), src i -> dst j
-    const int w = k / (H * H), i = (k / H) % H, j = k % H;
-    const float e = sv[w][i] + tv[w][j];
-    al[w][i][j] = e > 0.f ? e : 0.01f * e;
+  if constexpr (kWide) {
+    // softmax over all H^2 edges of the row's graph without keeping them.  lrelu and the
+    // sum s_i + t_j are monotone, so the largest edge is lrelu(max s + max t) exactly.
+    if (wv < W) {
+      const float a = wave_max(ln < H ? sv[wv][ln] : -INFINITY), c2 = wave_max(ln < H ? tv[wv][ln] : -INFINITY);
+      const float e = a + c2;
+      if (ln == 0) mx[wv] = e > 0.f ? e : 0.01f * e;
+    }
+    __syncthreads();
+    if (t < W * H) {  // sum_j exp(e_ij - max) of source i
+      const int w = t / H, i = t % H;
+      float s = 0.f;
+      for (int j = 0; j < H; ++j) {
+        const float e = sv[w][i] + tv[w][j];
+        s += expf((e > 0.f ? e : 0.01f * e) - mx[w]);
+      }
+      red[w][i] = s;
+    }
+    __syncthreads();
+    if (wv < W) {
+      const float s = wave_sum(ln < H ? red[wv][ln] : 0.f);
+      if (ln == 0) sm[wv] = s;
+    }
+    __syncthreads();
+    if (t < W * H) red[t / H][t % H] /= sm[t / H];  // column weight of source i: sum_j a_ij
+    __syncthreads();
+  } else {
+    for (int k = t; k < W * H * H; k += kFT) {  // e_ij = lrelu(a1.z_i + a2.z_j), src i -> dst j
+      const int w = k / (H * H), i = (k / H) % H, j = k % H;
+      const float e = sv[w][i] + tv[w][j];
+      al[w][i][j] = e > 0.f ? e : 0.01f * e;
+    }
+    __syncthreads();
+    if (t < W * H) {  // softmax over all H^2 edges of the row's graph: max, then sum
+      const int w = t / H, i = t % H;
+      float m = -INFINITY;
+      for (int j = 0; j < H; ++j) m = fmaxf(m, al[w][i][j]);
+      red[w][i] = m;
+    }
+    __syncthreads();
+    if (t < W) {
+      float m = -INFINITY;
+      for (int i = 0; i < H; ++i) m = fmaxf(m, red[t][i]);
+      mx[t] = m;
+    }
+    __syncthreads();
+    for (int k = t; k < W * H * H; k += kFT) {
+      const int w = k / (H * H), i = (k / H) % H, j = k % H;
+      al[w][i][j] = expf(al[w][i][j] - mx[w]);
+    }
+    __syncthreads();
+    if (t < W * H) {
+      const int w = t / H, i = t % H;
+      float s = 0.f;
+      for (int j = 0; j < H; ++j) s += al[w][i][j];
+      red[w][i] = s;
+    }
+    __syncthreads();
+    if (t < W) {
+      float s = 0.f;
+      for (int i = 0; i < H; ++i) s += red[t][i];
+      sm[t] = s;
+    }
+    __syncthreads();
+    for (int k = t; k < W * H * H; k += kFT) {
+      const int w = k / (H * H), i = (k / H) % H, j = k % H;
+      al[w][i][j] = al[w][i][j] / sm[w];
+    }
+    __syncthreads();
+    if (t < W * H) {  // column weight of source i: sum_j a_ij
+      const int w = t / H, i = t % H;
+      float s = 0.f;
+      for (int j = 0; j < H; ++j) s += al[w][i][j];
+      red[w][i] = s;
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  if (t < W * H) {  // softmax over all H^2 edges of the row's graph: max, then sum
-    const int w = t / H, i = t % H;
-    float m = -INFINITY;
-    for (int j = 0; j < H; ++j) m = fmaxf(m, al[w][i][j]);
-    red[w][i] = m;
-  }
-  __syncthreads();
-  if (t < W) {
-    float m = -INFINITY;
-    for (int i = 0; i < H; ++i) m = fmaxf(m, red[t][i]);
-    mx[t] = m;
-  }
-  __syncthreads();
-  for (int k = t; k < W * H * H; k += kFT) {
-    const int w = k / (H * H), i = (k / H) % H, j = k % H;
-    al[w][i][j] = expf(al[w][i][j] - mx[w]);
-  }
-  __syncthreads();
-  if (t < W * H) {
-    const int w = t / H, i = t % H;
-    float s = 0.f;
-    for (int j = 0; j < H; ++j) s += al[w][i][j];
-    red[w][i] = s;
-  }
-  __syncthreads();
-  if (t < W) {
-    float s = 0.f;
-    for (int i = 0; i < H; ++i) s += red[t][i];
-    sm[t] = s;
-  }
-  __syncthreads();
-  for (int k = t; k < W * H * H; k += kFT) {
-    const int w = k / (H * H), i = (k / H) % H, j = k % H;
-    al[w][i][j] = al[w][i][j] / sm[w];
-  }
-  __syncthreads();
-  if (t < W * H) {  // column weight of source i: sum_j a_ij
-    const int w = t / H, i = t % H;
-    float s = 0.f;
-    for (int j = 0; j < H; ++j) s += al[w][i][j];
-    red[w][i] = s;
-  }
-  __syncthreads();
   if (t < W * D) {  // gat_w[d] = mean_j sum_i a_ij z_i[d] = (1/H) sum_i red_i z_i[d]
     const int w = t / D, d = t % D;
     float s = 0.f;
@@ -188,7 +289,7 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
   }
   __syncthreads();
 
-  // ---- MultiheadAttention(19, 1 head) over the 3 rows ----
+  // ---- MultiheadAttention(E, 1 head) over the 3 rows ----
   for (int k = t; k < W * C::Q; k += kFT) {
     const int w = k / C::Q, o = k % C::Q;
     float a = P[C::INB + o];
@@ -225,11 +326,22 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
     fl[w * E + o] = a;
   }
   __syncthreads();
-  // ---- encoder Linear(57 -> 160) ----
-  if (t < C::NL) {
-    float a = P[C::ENCB + t];
-    for (int k = 0; k < C::NF; ++k) a = fmaf(P[C::ENC + t * C::NF + k], fl[k], a);
-    lat[t] = a;
+  // ---- encoder Linear(3E -> 10H) ----
+  if constexpr (kWide) {  // kSub lanes per output row, striding k: the row is read in 64-byte pieces
+    for (int base = 0; base < C::NL; base += kFT / kSub) {
+      const int r = base + sg;
+      float a = 0.f;
+      if (r < C::NL)
+        for (int k = sl; k < C::NF; k += kSub) a = fmaf(P[C::ENC + r * C::NF + k], fl[k], a);
+      a = sub_sum(a);
+      if (r < C::NL && sl == 0) lat[r] = P[C::ENCB + r] + a;
+    }
+  } else {
+    if (t < C::NL) {
+      float a = P[C::ENCB + t];
+      for (int k = 0; k < C::NF; ++k) a = fmaf(P[C::ENC + t * C::NF + k], fl[k], a);
+      lat[t] = a;
+    }
   }
   __syncthreads();
   // ---- per-host decoders ----
@@ -250,7 +362,7 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
     pr[t][1] = sigm(pr[t][1]);
   }
   __syncthreads();
-  if (!train) {
+  if constexpr (!TRAIN) {
     if (t < 2 * H) {
       probs_out[(long)b * 2 * H + t] = (double)an[t >> 1][t & 1];
       protos_out[(long)b * 2 * H + t] = (double)pr[t >> 1][t & 1];
@@ -301,15 +413,15 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
     else
       G[(which ? C::PRB : C::ANB) + o] = s;
   }
-  if (t < C::NL) {
-    const int h = t / L, l = t % L;
-    dlat[t] = P[C::AN + l] * dan[h][0] + P[C::AN + L + l] * dan[h][1] + P[C::PR + l] * dpr[h][0] +
+  for_items<C::NL>(t, [&](int k) {
+    const int h = k / L, l = k % L;
+    dlat[k] = P[C::AN + l] * dan[h][0] + P[C::AN + L + l] * dan[h][1] + P[C::PR + l] * dpr[h][0] +
               P[C::PR + L + l] * dpr[h][1];
-  }
+  });
   __syncthreads();
   // encoder
   for (int k = t; k < C::NL * C::NF; k += kFT) G[C::ENC + k] = dlat[k / C::NF] * fl[k % C::NF];
-  if (t < C::NL) G[C::ENCB + t] = dlat[t];
+  for_items<C::NL>(t, [&](int k) { G[C::ENCB + k] = dlat[k]; });
   if (t < C::NF) {
     float s = 0.f;
     for (int r = 0; r < C::NL; ++r) s = fmaf(P[C::ENC + r * C::NF + t], dlat[r], s);
@@ -346,13 +458,13 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
     for (int v = 0; v < W; ++v) dS[t][v] = pa[t][v] * (dP[t][v] - s) * isq;
   }
   __syncthreads();
-  if (t < 2 * W * E) {  // dq_w = sum_v dS[w][v] k_v; dk_v = sum_w dS[w][v] q_w
-    const int part = t / (W * E), w = (t / E) % W, e = t % E;
+  for_items<2 * W * E>(t, [&](int k) {  // dq_w = sum_v dS[w][v] k_v; dk_v = sum_w dS[w][v] q_w
+    const int part = k / (W * E), w = (k / E) % W, e = k % E;
     if (part == 0)
       dqkv[w][e] = dS[w][0] * qkv[0][E + e] + dS[w][1] * qkv[1][E + e] + dS[w][2] * qkv[2][E + e];
     else
       dqkv[w][E + e] = dS[0][w] * qkv[0][e] + dS[1][w] * qkv[1][e] + dS[2][w] * qkv[2][e];
-  }
+  });
   __syncthreads();
   // in_proj: dWin = sum_w dqkv_w c_w^T, dc_w = Win^T dqkv_w
   for (int k = t; k < C::Q * E; k += kFT) {
@@ -410,69 +522,138 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int train, int K, const f
 
   // ---- GAT backward: gat_w = (1/H) sum_i (sum_j a_ij) z_i ----
   // d a_ij = (1/H) z_i . dgat_w; d z_i = (1/H)(sum_j a_ij) dgat_w (+ the score terms)
-  for (int k = t; k < W * H * H; k += kFT) {
-    const int w = k / (H * H), i = (k / H) % H, j = k % H;
-    float s = 0.f;
-    for (int d = 0; d < D; ++d) s = fmaf(z[w][i][d], dc[w][3 + d], s);
-    dal[w][i][j] = s / (float)H;   // independent of j
-  }
-  __syncthreads();
-  if (t < W) {  // sum over edges of a . da
-    float s = 0.f;
-    for (int i = 0; i < H; ++i)
-      for (int j = 0; j < H; ++j) s = fmaf(al[t][i][j], dal[t][i][j], s);
-    sm[t] = s;
-  }
-  __syncthreads();
-  for (int k = t; k < W * H * H; k += kFT) {  // softmax backward, then the LeakyReLU
-    const int w = k / (H * H), i = (k / H) % H, j = k % H;
-    const float de = al[w][i][j] * (dal[w][i][j] - sm[w]);
-    const float e = sv[w][i] + tv[w][j];
-    dal[w][i][j] = e > 0.f ? de : 0.01f * de;
-  }
-  __syncthreads();
-  if (t < 2 * W * H) {  // d s_i = sum_j de_ij, d t_j = sum_i de_ij
-    const int half = t / (W * H), w = (t / H) % W, i = t % H;
-    float s = 0.f;
-    for (int k = 0; k < H; ++k) s += half ? dal[w][k][i] : dal[w][i][k];
-    (half ? dtv : dsv)[w][i] = s;
-  }
-  __syncthreads();
-  for (int k = t; k < W * H * D; k += kFT) {
-    const int w = k / (H * D), i = (k / D) % H, d = k % D;
-    dz[w][i][d] = red[w][i] / (float)H * dc[w][3 + d] + dsv[w][i] * P[C::ATT + d] + dtv[w][i] * P[C::ATT + D + d];
-  }
-  if (t < 2 * D) {  // attn_fc: sum over rows and nodes of (d s_i) z_i | (d t_j) z_j
-    const int half = t / D, d = t % D;
-    float s = 0.f;
-    for (int w = 0; w < W; ++w)
-      for (int i = 0; i < H; ++i) s = fmaf(half ? dtv[w][i] : dsv[w][i], z[w][i][d], s);
-    G[C::ATT + t] = s;
-  }
-  __syncthreads();
-  if (t < D * 3) {  // fc: sum over rows and nodes of dz_i x_i^T
-    const int d = t / 3, f = t % 3;
-    float s = 0.f;
-    for (int w = 0; w < W; ++w)
-      for (int i = 0; i < H; ++i) s = fmaf(dz[w][i][d], x[w][3 * i + f], s);
-    G[C::FC + t] = s;
+  if constexpr (kWide) {
+    if (t < W * H) {
+      const int w = t / H, i = t % H;
+      float s = 0.f;
+      for (int d = 0; d < D; ++d) s = fmaf(z[w][i][d], dc[w][3 + d], s);
+      dav[w][i] = s / (float)H;
+    }
+    __syncthreads();
+    if (wv < W) {  // sum over edges of a . da = sum_i (sum_j a_ij) da_i
+      const float s = wave_sum(ln < H ? red[wv][ln] * dav[wv][ln] : 0.f);
+      if (ln == 0) ss[wv] = s;
+    }
+    __syncthreads();
+    // softmax backward, the LeakyReLU, and d s_i = sum_j de_ij | d t_j = sum_i de_ij, the edge
+    // weights recomputed as the forward made them
+    for (int k = t; k < 2 * W * H; k += kFT) {
+      const int half = k / (W * H), w = (k / H) % W, n = k % H;
+      const float m = mx[w], inv = 1.f / sm[w], sw = ss[w];
+      float s = 0.f;
+      for (int q = 0; q < H; ++q) {
+        const int i = half ? q : n, j = half ? n : q;
+        const float e = sv[w][i] + tv[w][j];
+        const float de = expf((e > 0.f ? e : 0.01f * e) - m) * inv * (dav[w][i] - sw);
+        s += e > 0.f ? de : 0.01f * de;
+      }
+      (half ? dtv : dsv)[w][n] = s;
+    }
+    __syncthreads();
+    // attn_fc: sum over rows and nodes of (d s_i) z_i | (d t_j) z_j; fc: of dz_i x_i^T with
+    // dz_i = (1/H)(sum_j a_ij) dgat_w + (d s_i) a1 + (d t_i) a2 made in place; kSub lanes per output
+    for (int base = 0; base < 2 * D + 3 * D; base += kFT / kSub) {
+      const int o = base + sg;
+      float s = 0.f;
+      if (o < 2 * D) {
+        const int half = o / D, d = o % D;
+        for (int n = sl; n < W * H; n += kSub) {
+          const int w = n / H, i = n % H;
+          s = fmaf(half ? dtv[w][i] : dsv[w][i], z[w][i][d], s);
+        }
+      } else if (o < 5 * D) {
+        const int d = (o - 2 * D) / 3, f = (o - 2 * D) % 3;
+        const float a1 = P[C::ATT + d], a2 = P[C::ATT + D + d];
+        for (int n = sl; n < W * H; n += kSub) {
+          const int w = n / H, i = n % H;
+          const float dzv = red[w][i] / (float)H * dc[w][3 + d] + dsv[w][i] * a1 + dtv[w][i] * a2;
+          s = fmaf(dzv, x[w][3 * i + f], s);
+        }
+      }
+      s = sub_sum(s);
+      if (o < 5 * D && sl == 0) G[(o < 2 * D ? C::ATT : C::FC - 2 * D) + o] = s;
+    }
+  } else {
+    for (int k = t; k < W * H * H; k += kFT) {
+      const int w = k / (H * H), i = (k / H) % H, j = k % H;
+      float s = 0.f;
+      for (int d = 0; d < D; ++d) s = fmaf(z[w][i][d], dc[w][3 + d], s);
+      dal[w][i][j] = s / (float)H;   // independent of j
+    }
+    __syncthreads();
+    if (t < W) {  // sum over edges of a . da
+      float s = 0.f;
+      for (int i = 0; i < H; ++i)
+        for (int j = 0; j < H; ++j) s = fmaf(al[t][i][j], dal[t][i][j], s);
+      sm[t] = s;
+    }
+    __syncthreads();
+    for (int k = t; k < W * H * H; k += kFT) {  // softmax backward, then the LeakyReLU
+      const int w = k / (H * H), i = (k / H) % H, j = k % H;
+      const float de = al[w][i][j] * (dal[w][i][j] - sm[w]);
+      const float e = sv[w][i] + tv[w][j];
+      dal[w][i][j] = e > 0.f ? de : 0.01f * de;
+    }
+    __syncthreads();
+    if (t < 2 * W * H) {  // d s_i = sum_j de_ij, d t_j = sum_i de_ij
+      const int half = t / (W * H), w = (t / H) % W, i = t % H;
+      float s = 0.f;
+      for (int k = 0; k < H; ++k) s += half ? dal[w][k][i] : dal[w][i][k];
+      (half ? dtv : dsv)[w][i] = s;
+    }
+    __syncthreads();
+    for (int k = t; k < W * H * D; k += kFT) {
+      const int w = k / (H * D), i = (k / D) % H, d = k % D;
+      dz[w][i][d] = red[w][i] / (float)H * dc[w][3 + d] + dsv[w][i] * P[C::ATT + d] + dtv[w][i] * P[C::ATT + D + d];
+    }
+    if (t < 2 * D) {  // attn_fc: sum over rows and nodes of (d s_i) z_i | (d t_j) z_j
+      const int half = t / D, d = t % D;
+      float s = 0.f;
+      for (int w = 0; w < W; ++w)
+        for (int i = 0; i < H; ++i) s = fmaf(half ? dtv[w][i] : dsv[w][i], z[w][i][d], s);
+      G[C::ATT + t] = s;
+    }
+    __syncthreads();
+    if (t < D * 3) {  // fc: sum over rows and nodes of dz_i x_i^T
+      const int d = t / 3, f = t % 3;
+      float s = 0.f;
+      for (int w = 0; w < W; ++w)
+        for (int i = 0; i < H; ++i) s = fmaf(dz[w][i][d], x[w][3 * i + f], s);
+      G[C::FC + t] = s;
+    }
   }
 }
 
 }  // namespace
 
-int fpe_param_count() { return FP::SIZE; }
+int fpe_param_count(int H) { return H == 16 ? FP<16>::SIZE : H == 50 ? FP<50>::SIZE : 0; }
 
-hipError_t launch_fpe_step(const float* win, const float* h0, const int* y, const int* cls, const float* P, float* G,
-                           int K, double* state, double update_min, double decay, double* loss, hipStream_t st) {
-  fpe_step_kernel<<<1, kFT, 0, st>>>(1, K, win, h0, y, cls, P, G, state, update_min, decay, loss, nullptr, nullptr);
+// LDS is static in all four instantiations (below the 64 KB limit), so a launch needs no
+// per-device function attribute.
+hipError_t launch_fpe_step(int n_hosts, const float* win, const float* h0, const int* y, const int* cls,
+                           const float* P, float* G, int K, double* state, double update_min, double decay,
+                           double* loss, hipStream_t st) {
+  if (n_hosts == 16)
+    fpe_step_kernel<16, true><<<1, kFT, 0, st>>>(K, win, h0, y, cls, P, G, state, update_min, decay, loss, nullptr,
+                                                 nullptr);
+  else if (n_hosts == 50)
+    fpe_step_kernel<50, true><<<1, kFT, 0, st>>>(K, win, h0, y, cls, P, G, state, update_min, decay, loss, nullptr,
+                                                 nullptr);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-hipError_t launch_fpe_forward_many(int n, const float* wins, const float* h0s, const float* P, double* probs,
-                                   double* protos, hipStream_t st) {
-  fpe_step_kernel<<<n, kFT, 0, st>>>(0, 3, wins, h0s, nullptr, nullptr, P, nullptr, nullptr, 0.0, 0.0, nullptr, probs,
-                                     protos);
+hipError_t launch_fpe_forward_many(int n_hosts, int n, const float* wins, const float* h0s, const float* P,
+                                   double* probs, double* protos, hipStream_t st) {
+  if (n_hosts == 16)
+    fpe_step_kernel<16, false><<<n, kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr, nullptr, 0.0, 0.0,
+                                                  nullptr, probs, protos);
+  else if (n_hosts == 50)
+    fpe_step_kernel<50, false><<<n, kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr, nullptr, 0.0, 0.0,
+                                                  nullptr, probs, protos);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

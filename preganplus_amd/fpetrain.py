@@ -1,4 +1,6 @@
-"""Offline training of PreGAN's FPE_16 encoder on MI355X (PreGAN.py:26-27,
+"""Offline training of PreGAN's FPE encoder on MI355X, at 16 or 50 hosts
+(FPE_16, and FPE_16's architecture with its constants set for 50 hosts: the
+reference's own FPE_50 class cannot run) (PreGAN.py:26-27,
 39-49): with no FPE checkpoint the reference creates a new FPE_16 and trains it
 for num_epochs (train.py:42-57 backprop + :94-109 accuracy over utils.py:36-42
 load_dataset's series, AdamW lr 1e-4 weight decay 1e-5, models.py:14), saving
@@ -25,12 +27,13 @@ from . import weights as W
 from .train import PROTO_FACTOR_DECAY, PROTO_UPDATE_MIN, TuneState, _AdamTensor, accuracy_scores
 
 FPE_LR = 1e-4          # FPE_16.lr (models.py:14)
+SUPPORTED_H = (16, 50)  # the host counts pgp_fpetrain.hip is compiled for
 COND = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")   # no gradient without a positive label
 
 
 class FPETrainer:
-    """fp32 master weights, gradients and AdamW moments of FPE_16 on the device,
-    in state_dict order (weights.fpe_shapes)."""
+    """fp32 master weights, gradients and AdamW moments of the H-host FPE on the
+    device, in state_dict order (weights.fpe_shapes(H)); H in SUPPORTED_H."""
 
     def __init__(self, fpe: dict, device="cuda", state: dict | None = None, weight_decay=1e-5,
                  betas=(0.9, 0.999), eps=1e-8, H=16):
@@ -51,7 +54,8 @@ class FPETrainer:
             L._pgp_fpetrain_bound = True
         n = int(L.pgp_fpe_param_len(H))
         if n == 0:
-            raise ValueError(f"FPE training: H={H} not supported (FPE_16 only)")
+            raise ValueError(f"FPE training: H={H} not supported (supported host counts: "
+                             f"{', '.join(map(str, SUPPORTED_H))})")
         shapes = W.fpe_shapes(H)
         self.tensors, off = [], 0
         for name, shp in shapes.items():

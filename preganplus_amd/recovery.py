@@ -690,9 +690,11 @@ class PreGANRecovery(_SaveGan, Recovery):
         self.device = torch.device(device or "cuda")
         self.load_models(model_folder, weights, extra)
 
-    # -- PreGAN.py:22-37 (the encoder is frozen; no encoder training path: a
-    #    missing FPE checkpoint falls back to the packaged FPE_16 weights, and
-    #    the GAN checkpoints save_gan keeps rewriting are loaded over them) --
+    # -- PreGAN.py:22-37 (the encoder is frozen once loaded: a missing FPE
+    #    checkpoint falls back to the packaged FPE weights of that host count
+    #    where the package has them (16 hosts, simulator), with the GAN
+    #    checkpoints save_gan keeps rewriting loaded over them; with neither, a
+    #    new FPE is trained offline first, at 16 or 50 hosts: _load_new_model) --
     def load_models(self, model_folder=None, weights=None, extra=None):
         if weights is None:
             folder = model_folder or MODEL_FOLDER
@@ -740,7 +742,7 @@ class PreGANRecovery(_SaveGan, Recovery):
 
     def _load_new_model(self, folder):
         """load_model without a checkpoint (utils.py:76-78: epoch -1, a new
-        FPE_16 with torch's module initialisation distributions,
+        FPE (FPE_16's architecture at self.hosts) with torch's module initialisation distributions,
         weights.torch_default_fpe_weights, ``init_seed`` seeds it), train_model
         (PreGAN.py:39-49: num_epochs epochs of backprop + accuracy over
         load_dataset's whole data/<env>/time_series.npy, the FPE checkpoint

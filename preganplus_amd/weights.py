@@ -277,6 +277,15 @@ def weights_checksum(weights):
     return h + float(np.asarray(weights["prototypes"]).sum())
 
 
+def fpe_weights_checksum(weights):
+    """weights_checksum for a PreGAN (FPE) set: its FPE section and prototypes."""
+    h = 0.0
+    for k in sorted(weights["fpe"]):
+        a = np.asarray(weights["fpe"][k], dtype=np.float64).reshape(-1)
+        h += float(np.dot(a, np.cos(np.arange(a.size) * 0.001)))
+    return h + float(np.asarray(weights["prototypes"]).sum())
+
+
 _BUFFERS = {"transformer": ("pos_encoder.pe",), "fpe": (), "gen": (), "disc": ()}   # state_dict entries that are not parameters
 
 
