@@ -221,7 +221,8 @@ int pgp_forward_fpe_stage(pgp_model* m, int stage, int batch, const float* windo
  * Master weights `P` are fp32 in the NATURAL blob order of pgp_load_weights
  * (transformer | gen | disc, prototypes excluded); grads `G` share the layout.
  * Replace, per window (or summed over a batch of windows):
- *   pgp_tune_forward   Transformer forward in train mode (dropout p=0),
+ *   pgp_tune_forward   Transformer forward in train mode (dropout p=0; live
+ *                      dropout: pgp_tune_step1_dropout, 8 / 16 hosts),
  *                      models.py:376-416, saving activations in `scratch`
  *   pgp_tune_backward  custom_loss / triplet_loss gradients (train.py:13-40;
  *                      the sequential prototype/counter logic stays on the host
@@ -350,6 +351,38 @@ int pgp_tune_targets(int n_hosts, int n_protos, const float* logits, const float
 int pgp_tune_step1(int n_hosts, int n_protos, const float* window, const int* y, const int* cls, const float* P,
                    float* G, double* state, double update_min, double decay, float* logits, float* protos,
                    double* loss, void* stream);
+/* Train-mode dropout for that step (models.py:300,311,354: the reference never
+ * calls eval(), so tune_model / train_model run with p = 0.1 live at the
+ * positional encoding, the attention probabilities, dropout1, the feed-forward
+ * dropout and dropout2 of both layers).  The masks are this library's own,
+ * counter-based and fully specified: Philox4x32-10, key =
+ * (seed_lo, seed_hi), counter = (e >> 2, site, n_lo, n_hi) for element e of
+ * a site in optimizer step n, output word e & 3; dropped iff word <
+ * (uint32)(p * 2^32) (the product in double), kept elements scaled by
+ * 1/(1-p) in fp32.  Sites in order, with token t = w*H + h: 0 PE output
+ * [t*H + c]; then per layer l: 1+4l attention probabilities
+ * [(t*2 + head)*3 + key_step], 2+4l out_proj output [t*H + c], 3+4l
+ * relu(linear1) [t*64 + k], 4+4l linear2 output [t*H + c].
+ * rng_device: two unsigned long long on the device, {seed, base step}; the
+ * step's n = base step + `step` (>= 0; a launch constant, so a captured graph
+ * of i = 0.. steps replays with a fresh base).  n_hosts 8 or 16, else
+ * PGP_ERR_UNSUPPORTED; p in [0, 1), else PGP_ERR_ARG.
+ * pgp_tune_dropout_mask_len (models.py:300,311,354): elements of one step's
+ * masks, 10560 at 16 hosts, 4320 at 8; 0 if unsupported. */
+size_t pgp_tune_dropout_mask_len(int n_hosts);
+/* pgp_tune_step1 with those masks applied in the forward and the backward
+ * (models.py:300,311,354).  p == 0 launches pgp_tune_step1's kernel: the same
+ * bits, rng_device unread.  Deterministic: the same (seed, base, step) and
+ * inputs give the same bits in every output. */
+int pgp_tune_step1_dropout(int n_hosts, int n_protos, const float* window, const int* y, const int* cls,
+                           const float* P, float* G, double* state, double update_min, double decay, float* logits,
+                           float* protos, double* loss, float p, const unsigned long long* rng_device, int step,
+                           void* stream);
+/* The keep bytes that step would use (models.py:300,311,354; the test tap: the
+ * device function the step kernel fills its masks with): keep [mask_len]
+ * bytes on the device, 4-byte aligned, 1 = kept, in the site order above. */
+int pgp_tune_dropout_masks(int n_hosts, float p, const unsigned long long* rng_device, int step, unsigned char* keep,
+                           void* stream);
 /* n independent batch-1 tuning forwards from the master P (n_hosts 8 or 16;
  * one workgroup per window, the forward of pgp_tune_step1): the batched
  * model(windows) that accuracy() scores (train.py:94-109, PreGANPlus.py:56).

@@ -519,6 +519,48 @@ int pgp_tune_step1(int n_hosts, int n_protos, const float* window, const int* y,
   return PGP_OK;
 }
 
+size_t pgp_tune_dropout_mask_len(int n_hosts) { return tune1_dropout_mask_len(n_hosts); }
+
+namespace {
+// dropped iff word < (uint32)(p * 2^32), the product in double; p in [0, 1)
+inline bool drop_threshold(float p, unsigned int* thr) {
+  if (!(p >= 0.f && p < 1.f)) return false;
+  *thr = (unsigned int)((double)p * 4294967296.0);
+  return true;
+}
+}  // namespace
+
+int pgp_tune_step1_dropout(int n_hosts, int n_protos, const float* window, const int* y, const int* cls, const float* P,
+                           float* G, double* state, double update_min, double decay, float* logits, float* protos,
+                           double* loss, float p, const unsigned long long* rng_device, int step, void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (fused step with dropout: 8 or 16)");
+  unsigned int thr = 0;
+  if (!drop_threshold(p, &thr)) return fail(PGP_ERR_ARG, "dropout p outside [0, 1)");
+  if (n_protos < 3) return fail(PGP_ERR_ARG, "triplet_loss needs prototypes 0-2");
+  if (!window || !y || !cls || !P || !G || !state || !logits || !protos || !loss || step < 0)
+    return fail(PGP_ERR_ARG, "bad tune_step1_dropout arguments");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (thr == 0) {  // nothing can be dropped: pgp_tune_step1 itself, bit for bit
+    HIPCHK(launch_tune1(n_hosts, n_protos, window, y, cls, P, G, state, update_min, decay, logits, protos, loss, st));
+    return PGP_OK;
+  }
+  if (!rng_device) return fail(PGP_ERR_ARG, "dropout needs rng_device = {seed, base step}");
+  HIPCHK(launch_tune1_dropout(n_hosts, n_protos, window, y, cls, P, G, state, update_min, decay, logits, protos, loss,
+                              thr, 1.0f / (1.0f - p), rng_device, step, st));
+  return PGP_OK;
+}
+
+int pgp_tune_dropout_masks(int n_hosts, float p, const unsigned long long* rng_device, int step, unsigned char* keep,
+                           void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (dropout masks: 8 or 16)");
+  unsigned int thr = 0;
+  if (!drop_threshold(p, &thr)) return fail(PGP_ERR_ARG, "dropout p outside [0, 1)");
+  if (!rng_device || !keep || step < 0 || (reinterpret_cast<uintptr_t>(keep) & 3))
+    return fail(PGP_ERR_ARG, "bad tune_dropout_masks arguments (keep: 4-byte aligned)");
+  HIPCHK(launch_drop_masks(n_hosts, thr, rng_device, step, keep, reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
 int pgp_tune_forward_many(int n_hosts, int n_windows, const float* windows, const float* P, double* logits,
                           double* protos, void* stream) {
   if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (fused forward: 8 or 16)");

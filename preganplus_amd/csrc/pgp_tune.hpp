@@ -103,6 +103,17 @@ bool tune1_supported(int H);
 hipError_t launch_tune1(int H, int K, const float* win, const int* y, const int* cls, const float* P, float* G,
                         double* state, double update_min, double decay, float* logits, float* protos, double* loss,
                         hipStream_t st);
+// the same step with train-mode dropout (pgp_philox.hpp): element dropped iff
+// its Philox word < thr, kept ones scaled by ks; rng = {seed, base step} on the
+// device, masks of optimizer step rng[1] + step.  launch_drop_masks writes that
+// step's keep bytes [tune1_dropout_mask_len(H)] (4-byte aligned, 1 = kept).
+size_t tune1_dropout_mask_len(int H);
+hipError_t launch_tune1_dropout(int H, int K, const float* win, const int* y, const int* cls, const float* P, float* G,
+                                double* state, double update_min, double decay, float* logits, float* protos,
+                                double* loss, unsigned int thr, float ks, const unsigned long long* rng, int step,
+                                hipStream_t st);
+hipError_t launch_drop_masks(int H, unsigned int thr, const unsigned long long* rng, int step, unsigned char* keep,
+                             hipStream_t st);
 // n independent batch-1 forwards (accuracy()'s batch), fp64 logits / protos [n][H][2]
 hipError_t launch_fwd_many(int H, int n, const float* win, const float* P, double* logits, double* protos,
                            hipStream_t st);

@@ -30,6 +30,7 @@
 
 #include "pgp_device.hpp"
 #include "pgp_gemm.hpp"
+#include "pgp_philox.hpp"
 #include "pgp_train.hpp"
 #include "pgp_tunetargets.hpp"
 
@@ -93,16 +94,21 @@ struct T1 {
   static constexpr int WN = (int)(G::LAY0 + 2 * G::L_SIZE);  // GAT, time encoder, pe, both layers
   static constexpr int S_PW = S_GSX + 24;          // LDS copy of those weights
   static constexpr int TOTAL = S_PW + WN;
+  // train-mode dropout (DROP kernels only): one step's keep bytes after everything else
+  static constexpr int S_MK = TOTAL;
+  static constexpr int TOTAL_DROP = TOTAL + DropGeo<H>::TOTAL / 4;
   static_assert(S_CE % 2 == 0, "fp64 scratch alignment");
-  static_assert(TOTAL * 4 <= 160 * 1024, "LDS budget");
+  static_assert(TOTAL_DROP * 4 <= 160 * 1024, "LDS budget");
   static_assert(L % 64 == 0 && NO <= 64, "decoder wave mapping");
 };
 
 // y[t][n] = b[n] + sum_k W[n][k] act(x[t][k]) (+ R[t][n]) for t < T, n < N;
-// lanes run over tokens (odd strides: conflict-free), W is a broadcast
-template <int K, bool RELU>
+// lanes run over tokens (odd strides: conflict-free), W is a broadcast.
+// DROP: the linear's output is dropped before the residual is added
+// (keep[t*N + n], kept elements scaled by ks)
+template <int K, bool RELU, bool DROP = false>
 PGP_DEV void t1_linear(const float* W, const float* b, const float* x, int xs, int T, int N, float* y, int ys,
-                       const float* R, int rs, int tid) {
+                       const float* R, int rs, int tid, const unsigned char* keep = nullptr, float ks = 1.f) {
   for (int i = tid; i < T * N; i += kT1Threads) {
     const int n = i / T, t = i - n * T;
     float acc = b[n];
@@ -110,6 +116,7 @@ PGP_DEV void t1_linear(const float* W, const float* b, const float* x, int xs, i
     const float* xr = x + t * xs;
 #pragma unroll 16
     for (int k = 0; k < K; ++k) acc = fmaf(w[k], RELU ? fmaxf(xr[k], 0.f) : xr[k], acc);
+    if constexpr (DROP) acc = keep[t * N + n] ? acc * ks : 0.f;
     if (R) acc += R[t * rs + n];
     y[t * ys + n] = acc;
   }
@@ -141,10 +148,12 @@ PGP_DEV void t1_ln(const float* z, int T, const float* gam, const float* bet, fl
 }
 
 // LayerNorm backward: dy [T][DS] -> dx (in place), gamma / beta grads summed
-// over the T tokens (written to global)
-template <int D, int DS>
+// over the T tokens (written to global).  DROP: also dm = dx * (keep ? ks : 0),
+// the gradient entering the dropped residual branch (keep[t*D + c])
+template <int D, int DS, bool DROP = false>
 PGP_DEV void t1_ln_bwd(float* dy, const float* xh, const float* rs, const float* gam, int T, float* __restrict__ gg,
-                       float* __restrict__ gb, int tid) {
+                       float* __restrict__ gb, int tid, float* dm = nullptr, const unsigned char* keep = nullptr,
+                       float ks = 1.f) {
   for (int c = tid; c < D; c += kT1Threads) {  // parameter grads first (dy still the output grad)
     float sw = 0.f, sb = 0.f;
     for (int t = 0; t < T; ++t) {
@@ -169,7 +178,11 @@ PGP_DEV void t1_ln_bwd(float* dy, const float* xh, const float* rs, const float*
     s2 /= (float)D;
     const float r = rs[t];
 #pragma unroll
-    for (int c = 0; c < D; ++c) d[c] = r * (d[c] * gam[c] - s1 - x[c] * s2);
+    for (int c = 0; c < D; ++c) {
+      const float v = r * (d[c] * gam[c] - s1 - x[c] * s2);
+      d[c] = v;
+      if constexpr (DROP) dm[t * DS + c] = keep[t * D + c] ? v * ks : 0.f;
+    }
   }
 }
 
@@ -195,10 +208,14 @@ PGP_DEV void t1_dw(const float* dy, int dys, int N, const float* x, int xs, int 
     }
 }
 
-// dx[t][k] = sum_n W[n][k] dy[t][n] (+ R[t][k]); optional ReLU mask (m[t][k] > 0)
-template <int N>
+// dx[t][k] = sum_n W[n][k] dy[t][n] (+ R[t][k]); optional ReLU mask (m[t][k] > 0).
+// DROP: a masked element that passes is scaled by ks (the feed-forward
+// dropout, whose keep bits the stored pre-activation already carries), and
+// with `keep` the result is dropped as the forward dropped dx's activation
+// (keep[t*K + k])
+template <int N, bool DROP = false>
 PGP_DEV void t1_dx(const float* W, int K, const float* dy, int dys, int T, float* dx, int dxs, const float* R,
-                   int rs, const float* mask, int ms, int tid) {
+                   int rs, const float* mask, int ms, int tid, float ks = 1.f, const unsigned char* keep = nullptr) {
   for (int i = tid; i < T * K; i += kT1Threads) {
     const int t = i / K, k = i - t * K;
     float acc = 0.f;
@@ -206,7 +223,12 @@ PGP_DEV void t1_dx(const float* W, int K, const float* dy, int dys, int T, float
 #pragma unroll 16
     for (int n = 0; n < N; ++n) acc = fmaf(W[n * K + k], d[n], acc);
     if (R) acc += R[t * rs + k];
-    if (mask) acc = mask[t * ms + k] > 0.f ? acc : 0.f;
+    if constexpr (DROP) {
+      if (mask) acc = mask[t * ms + k] > 0.f ? acc * ks : 0.f;
+      if (keep) acc = keep[t * K + k] ? acc * ks : 0.f;
+    } else {
+      if (mask) acc = mask[t * ms + k] > 0.f ? acc : 0.f;
+    }
     dx[t * dxs + k] = acc;
   }
 }
@@ -215,12 +237,26 @@ PGP_DEV void t1_dx(const float* W, int K, const float* dy, int dys, int T, float
 // activation left in LDS (T1<H> layout) for the backward; the decoder outputs
 // (logits | sigmoid protos) end in sm[S_OUT] and, when given, in global memory.
 // Shared by the tuning step (tune1_kernel) and the batch-1 inference (infer1_kernel).
-template <int H>
+// DROP (the train-mode step only): the five dropout sites of models.py:300,311,354
+// from the step's keep bytes at sm[S_MK], filled here before the first barrier
+// (drop.thr / drop.ks: threshold and 1/(1-p); the Philox blocks run while the
+// weight copy's loads are in flight).
+struct T1Drop {
+  unsigned int thr;
+  float ks;
+  unsigned long long seed, step;
+};
+
+template <int H, bool DROP = false>
 PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __restrict__ win,
                         float* __restrict__ logits_out, float* __restrict__ protos_out, int& mk_,
-                        double* __restrict__ logits64 = nullptr, double* __restrict__ protos64 = nullptr) {
+                        double* __restrict__ logits64 = nullptr, double* __restrict__ protos64 = nullptr,
+                        T1Drop drop = T1Drop{}) {
   using S = T1<H>;
   using G = TGeo<H>;
+  using DG = DropGeo<H>;
+  [[maybe_unused]] const unsigned char* keep = reinterpret_cast<const unsigned char*>(sm + S::S_MK);
+  [[maybe_unused]] const float ks = drop.ks;
   constexpr int D = S::D, T = S::T, HD = S::HD, FF = S::FF, Q3 = S::Q3, NO = S::NO, L = S::L;
   constexpr int DS = S::DS, QS = S::QS, FS = S::FS;
   (void)mk_;
@@ -236,6 +272,9 @@ PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __r
   float* Pw = sm + S::S_PW;
   for (int i = tid; i < S::WN; i += kT1Threads) Pw[i] = P[i];
   for (int i = tid; i < 9 * H; i += kT1Threads) win_s[i] = win[i];
+  if constexpr (DROP)
+    drop_fill_masks<H>(reinterpret_cast<unsigned char*>(sm + S::S_MK), drop.thr, drop.seed, drop.step, tid,
+                       kT1Threads);
   T1SYNC();
   if (tid < 6) {  // u = fc^T a_src, v = fc^T a_dst (dlutils.py:315-329, algebraically)
     const int k = tid % 3;
@@ -301,7 +340,9 @@ PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __r
     const float* gr = g + t * DS;
 #pragma unroll
     for (int k = 0; k < D; ++k) acc = fmaf(wr[k], gr[k], acc);
-    xs[t * DS + c] = acc + Pw[G::PE + (t / H) * D + c];
+    acc += Pw[G::PE + (t / H) * D + c];
+    if constexpr (DROP) acc = keep[DG::O_PE + t * D + c] ? acc * ks : 0.f;  // pos_encoder's dropout (models.py:300)
+    xs[t * DS + c] = acc;
   }
   T1SYNC();
   const float scale = 1.0f / sqrtf((float)HD);
@@ -346,17 +387,25 @@ PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __r
       const float* p = pr + t * 6 + hh * 3;
       float acc = 0.f;
 #pragma unroll
-      for (int w2 = 0; w2 < 3; ++w2) acc = fmaf(p[w2], qkv[(w2 * H + h) * QS + 2 * D + c], acc);
+      for (int w2 = 0; w2 < 3; ++w2) {
+        float pv = p[w2];  // pr keeps the softmax itself (its backward); the product takes the dropped one
+        if constexpr (DROP) pv = keep[DG::o_at(l) + t * 6 + hh * 3 + w2] ? pv * ks : 0.f;
+        acc = fmaf(pv, qkv[(w2 * H + h) * QS + 2 * D + c], acc);
+      }
       o[t * DS + c] = acc;
     }
     T1SYNC();
-    t1_linear<D, false>(Lp + G::L_OUT, Lp + G::L_OUTB, o, DS, T, D, z, DS, x, DS, tid);  // out_proj + residual
+    // out_proj (dropout1) + residual
+    t1_linear<D, false, DROP>(Lp + G::L_OUT, Lp + G::L_OUTB, o, DS, T, D, z, DS, x, DS, tid, keep + DG::o_d1(l), ks);
     T1SYNC();
     t1_ln<D, DS>(z, T, Lp + G::L_N1W, Lp + G::L_N1B, xh1, rs1, y1, tid);
     T1SYNC();
-    t1_linear<D, false>(Lp + G::L_W1, Lp + G::L_B1, y1, DS, T, FF, f, FS, nullptr, 0, tid);
+    // DROP: f = linear1 * (keep ? ks : 0), so relu(f) is the dropped activation and f > 0 its backward mask
+    t1_linear<D, false, DROP>(Lp + G::L_W1, Lp + G::L_B1, y1, DS, T, FF, f, FS, nullptr, 0, tid, keep + DG::o_ff(l),
+                              ks);
     T1SYNC();
-    t1_linear<FF, true>(Lp + G::L_W2, Lp + G::L_B2, f, FS, T, D, z, DS, y1, DS, tid);  // linear2(relu f) + y1
+    // linear2(relu f) (dropout2) + y1
+    t1_linear<FF, true, DROP>(Lp + G::L_W2, Lp + G::L_B2, f, FS, T, D, z, DS, y1, DS, tid, keep + DG::o_d2(l), ks);
     T1SYNC();
     t1_ln<D, DS>(z, T, Lp + G::L_N2W, Lp + G::L_N2B, xh2, rs2, x + T * DS, tid);
     T1SYNC();
@@ -397,18 +446,25 @@ PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __r
   T1SYNC();
 }
 
-template <int H>
+// DROP (pgp_tune_step1_dropout, p > 0): train-mode dropout at the reference's
+// five sites; the masks of optimizer step rng[1] + step under seed rng[0]
+// (device memory: the step replays from a captured graph), thr / ks as T1Drop.
+template <int H, bool DROP>
 __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* __restrict__ win,
                                                            const int* __restrict__ yv, const int* __restrict__ cv,
                                                            const float* __restrict__ P, float* __restrict__ Gd,
                                                            double* __restrict__ state, double update_min,
                                                            double decay, float* __restrict__ logits_out,
-                                                           float* __restrict__ protos_out, double* __restrict__ loss) {
+                                                           float* __restrict__ protos_out, double* __restrict__ loss,
+                                                           unsigned int thr, float ks,
+                                                           const unsigned long long* __restrict__ rng, int step) {
   using S = T1<H>;
   using G = TGeo<H>;
+  using DG = DropGeo<H>;
   constexpr int D = S::D, T = S::T, HD = S::HD, FF = S::FF, Q3 = S::Q3, NO = S::NO, L = S::L;
   constexpr int DS = S::DS, QS = S::QS, FS = S::FS;
-  __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
+  __shared__ __attribute__((aligned(16))) float sm[DROP ? S::TOTAL_DROP : S::TOTAL];
+  [[maybe_unused]] const unsigned char* keep = reinterpret_cast<const unsigned char*>(sm + S::S_MK);
   const int tid = threadIdx.x;
   float* win_s = sm + S::S_WIN;
   float* st = sm + S::S_ST;
@@ -431,7 +487,11 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
     ys[i] = yv[i];
     cs[i] = cv[i];
   }
-  t1_forward<H>(sm, P, win, logits_out, protos_out, mk_);
+  if constexpr (DROP)
+    t1_forward<H, true>(sm, P, win, logits_out, protos_out, mk_, nullptr, nullptr,
+                        T1Drop{thr, ks, rng[0], rng[1] + (unsigned long long)step});
+  else
+    t1_forward<H, false>(sm, P, win, logits_out, protos_out, mk_);
   const float* x2 = xs + 2 * T * DS;
   float* out = sm + S::S_OUT;
   const float scale = 1.0f / sqrtf((float)HD);
@@ -494,18 +554,25 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
     const float* xh2 = sm + S::S_XH2 + l * T * DS;
     const float* rs2 = sm + S::S_RS2 + l * T;
     // norm2 backward: da (grad of the layer output) -> grad of z2 = y1 + ffn
-    t1_ln_bwd<D, DS>(da, xh2, rs2, Lp + G::L_N2W, T, Lg + G::L_N2W, Lg + G::L_N2B, tid);
+    // (DROP: dm = that gradient through dropout2, the one linear2 sees; dq is free here)
+    float* dm = DROP ? dq : da;
+    t1_ln_bwd<D, DS, DROP>(da, xh2, rs2, Lp + G::L_N2W, T, Lg + G::L_N2W, Lg + G::L_N2B, tid, dm,
+                           keep + DG::o_d2(l), ks);
     T1SYNC();
-    t1_dw<FF, true>(da, DS, D, f, FS, T, Lg + G::L_W2, Lg + G::L_B2, tid);         // linear2
-    t1_dx<D>(Lp + G::L_W2, FF, da, DS, T, df, FS, nullptr, 0, f, FS, tid);         // d relu(f) (mask f > 0)
+    t1_dw<FF, true>(dm, DS, D, f, FS, T, Lg + G::L_W2, Lg + G::L_B2, tid);         // linear2
+    // d relu(f) (mask f > 0; DROP: f carries the feed-forward dropout's keep bits, kept ones scaled)
+    t1_dx<D, DROP>(Lp + G::L_W2, FF, dm, DS, T, df, FS, nullptr, 0, f, FS, tid, ks);
     T1SYNC();
     t1_dw<D, false>(df, FS, FF, y1, DS, T, Lg + G::L_W1, Lg + G::L_B1, tid);       // linear1
     t1_dx<FF>(Lp + G::L_W1, D, df, FS, T, db, DS, da, DS, nullptr, 0, tid);        // dy1 = W1^T df + dz2
     T1SYNC();
-    t1_ln_bwd<D, DS>(db, xh1, rs1, Lp + G::L_N1W, T, Lg + G::L_N1W, Lg + G::L_N1B, tid);  // -> grad of z1
+    // -> grad of z1 (DROP: dm = it through dropout1, the one out_proj sees)
+    dm = DROP ? dq : db;
+    t1_ln_bwd<D, DS, DROP>(db, xh1, rs1, Lp + G::L_N1W, T, Lg + G::L_N1W, Lg + G::L_N1B, tid, dm,
+                           keep + DG::o_d1(l), ks);
     T1SYNC();
-    t1_dw<D, false>(db, DS, D, o, DS, T, Lg + G::L_OUT, Lg + G::L_OUTB, tid);      // out_proj
-    t1_dx<D>(Lp + G::L_OUT, D, db, DS, T, da, DS, nullptr, 0, nullptr, 0, tid);    // d o
+    t1_dw<D, false>(dm, DS, D, o, DS, T, Lg + G::L_OUT, Lg + G::L_OUTB, tid);      // out_proj
+    t1_dx<D>(Lp + G::L_OUT, D, dm, DS, T, da, DS, nullptr, 0, nullptr, 0, tid);    // d o
     T1SYNC();
     for (int i = tid; i < H * 2 * HD; i += kT1Threads) {  // attention backward per (host, head, e)
       const int h = i / (2 * HD), hh = (i / HD) % 2, e = i % HD;
@@ -520,6 +587,15 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
 #pragma unroll
         for (int w2 = 0; w2 < 3; ++w2) p[w][w2] = pr[(w * H + h) * 6 + hh * 3 + w2];
       }
+      // DROP: mk = keep ? ks : 0 per probability: dropped P = p * mk feeds P v, dP comes back through mk,
+      // the softmax backward itself uses the undropped p
+      [[maybe_unused]] float mk[3][3];
+      if constexpr (DROP) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+#pragma unroll
+          for (int w2 = 0; w2 < 3; ++w2) mk[w][w2] = keep[DG::o_at(l) + (w * H + h) * 6 + hh * 3 + w2] ? ks : 0.f;
+      }
       float dS[3][3];
 #pragma unroll
       for (int w = 0; w < 3; ++w) {
@@ -531,6 +607,7 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
           for (int e2 = 0; e2 < HD; ++e2)
             a = fmaf(da[(w * H + h) * DS + hh * HD + e2], qkv[(w2 * H + h) * QS + 2 * D + hh * HD + e2], a);
           dp[w2] = a;
+          if constexpr (DROP) dp[w2] *= mk[w][w2];
         }
         const float sd = p[w][0] * dp[0] + p[w][1] * dp[1] + p[w][2] * dp[2];
 #pragma unroll
@@ -541,12 +618,17 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
         float* rr = dq + (w * H + h) * QS + hh * HD + e;
         rr[0] = dS[w][0] * k[0] + dS[w][1] * k[1] + dS[w][2] * k[2];
         rr[D] = dS[0][w] * q[0] + dS[1][w] * q[1] + dS[2][w] * q[2];
-        rr[2 * D] = p[0][w] * dov[0] + p[1][w] * dov[1] + p[2][w] * dov[2];
+        if constexpr (DROP)
+          rr[2 * D] = p[0][w] * mk[0][w] * dov[0] + p[1][w] * mk[1][w] * dov[1] + p[2][w] * mk[2][w] * dov[2];
+        else
+          rr[2 * D] = p[0][w] * dov[0] + p[1][w] * dov[1] + p[2][w] * dov[2];
       }
     }
     T1SYNC();
     t1_dw<D, false>(dq, QS, Q3, x, DS, T, Lg + G::L_IN, Lg + G::L_INB, tid);       // in_proj
-    t1_dx<Q3>(Lp + G::L_IN, D, dq, QS, T, da, DS, db, DS, nullptr, 0, tid);        // Win^T dqkv + dz1 (residual)
+    // Win^T dqkv + dz1 (residual); DROP, layer 0: through the positional encoding's dropout
+    t1_dx<Q3, DROP>(Lp + G::L_IN, D, dq, QS, T, da, DS, db, DS, nullptr, 0, tid, ks,
+                    DROP && l == 0 ? keep + DG::O_PE : nullptr);
     T1SYNC();
   }
   // time encoder: da = grad of X0
@@ -837,11 +919,59 @@ hipError_t launch_tune1(int H, int K, const float* win, const int* y, const int*
                         hipStream_t st) {
   switch (H) {
     case 8:
-      tune1_kernel<8><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos, loss);
+      tune1_kernel<8, false><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos,
+                                                       loss, 0u, 1.f, nullptr, 0);
       break;
     case 16:
-      tune1_kernel<16><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos,
-                                                  loss);
+      tune1_kernel<16, false><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos,
+                                                        loss, 0u, 1.f, nullptr, 0);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// the step with train-mode dropout (thr > 0): tune1_kernel<H, true>
+hipError_t launch_tune1_dropout(int H, int K, const float* win, const int* y, const int* cls, const float* P, float* G,
+                                double* state, double update_min, double decay, float* logits, float* protos,
+                                double* loss, unsigned int thr, float ks, const unsigned long long* rng, int step,
+                                hipStream_t st) {
+  switch (H) {
+    case 8:
+      tune1_kernel<8, true><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos,
+                                                      loss, thr, ks, rng, step);
+      break;
+    case 16:
+      tune1_kernel<16, true><<<1, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay, logits, protos,
+                                                       loss, thr, ks, rng, step);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// the test tap: one step's keep bytes [DropGeo<H>::TOTAL] from the device function the step kernel fills its LDS with
+template <int H>
+__global__ __launch_bounds__(kT1Threads) void drop_masks_kernel(unsigned int thr,
+                                                                const unsigned long long* __restrict__ rng, int step,
+                                                                unsigned char* __restrict__ keep) {
+  drop_fill_masks<H>(keep, thr, rng[0], rng[1] + (unsigned long long)step, threadIdx.x, kT1Threads);
+}
+
+size_t tune1_dropout_mask_len(int H) {
+  return H == 8 ? (size_t)DropGeo<8>::TOTAL : H == 16 ? (size_t)DropGeo<16>::TOTAL : 0;
+}
+
+hipError_t launch_drop_masks(int H, unsigned int thr, const unsigned long long* rng, int step, unsigned char* keep,
+                             hipStream_t st) {
+  switch (H) {
+    case 8:
+      drop_masks_kernel<8><<<1, kT1Threads, 0, st>>>(thr, rng, step, keep);
+      break;
+    case 16:
+      drop_masks_kernel<16><<<1, kT1Threads, 0, st>>>(thr, rng, step, keep);
       break;
     default:
       return hipErrorInvalidValue;

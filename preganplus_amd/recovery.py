@@ -23,10 +23,15 @@ reference's ``save_gan`` does (PreGANPlus.py:76-81, utils.py:86-88), into the
 folder the models were loaded from (default ``recovery/PreGANSrc/checkpointsplus``,
 constants.py:3), off the critical path: a device-to-host copy on a side
 stream and ``torch.save`` on a writer thread (``_GanCheckpointWriter``).
-Deliberate deviations: dropout is off (the reference runs its
-modules in train mode with p=0.1, so its own decisions are stochastic); no
-plotting; a plugin built from injected ``weights=`` (tests, benches) writes
-only when ``save_folder`` is given.
+Dropout: the reference never calls ``eval()``, so its
+``tune_model`` / ``train_model`` train with the Transformer's p = 0.1 dropout
+live.  ``PreGANPlusRecovery(..., dropout=0.1, dropout_seed=s)`` trains the same
+way at 8 / 16 hosts, with this package's own counter-based masks (a function of
+the seed and the optimizer step: reproducible, resumable); the default
+``dropout=0`` is the deterministic step.  Detection (``run_model``'s forward)
+and ``accuracy()`` never drop, where the reference's own are stochastic.
+Deliberate deviations: no plotting; a plugin built from injected
+``weights=`` (tests, benches) writes only when ``save_folder`` is given.
 
 ``PreGANRecovery`` (``recovery/PreGAN.py:11-126``, BASELINE config C4): frozen
 FPE_16 encoder + K = 3 prototypes (HIP kernel K4), PreGAN's own Gen/Disc (K3),
@@ -99,9 +104,14 @@ class _SaveGan:
 
 class PreGANPlusRecovery(_SaveGan, Recovery):
     def __init__(self, hosts, env, training=False, device=None, model_folder=None, save_folder=_AUTO,
-                 weights=None, extra=None, init_seed=0):
+                 weights=None, extra=None, init_seed=0, dropout=0.0, dropout_seed=0):
         super().__init__()
         self.init_seed = int(init_seed)   # seeds a fresh model's initialisation (no checkpoint, no packaged weights)
+        # train-mode dropout of tune_model / train_model (models.py:300,311,354: the reference's p is 0.1)
+        self.dropout, self.dropout_seed = float(dropout), int(dropout_seed)
+        if self.dropout > 0 and hosts not in TR.FUSED_STEP_HOSTS:
+            raise ValueError(f"dropout > 0 is supported at {TR.FUSED_STEP_HOSTS} hosts (the fused batch-1 tuning "
+                             f"step), not {hosts}")
         self.model_name = f"Transformer_{hosts}"
         self.gen_name = f"Gen_{hosts}"
         self.disc_name = f"Disc_{hosts}"
@@ -145,7 +155,8 @@ class PreGANPlusRecovery(_SaveGan, Recovery):
         self.prototypes = np.asarray(weights["prototypes"], dtype=np.float64)
         self._infer = DecisionModel(self.hosts, weights, device=self.device)
         self._infer_stale = False
-        self.trainer = TR.Trainer(self.hosts, weights, self.extra, device=self.device)
+        self.trainer = TR.Trainer(self.hosts, weights, self.extra, device=self.device, dropout=self.dropout,
+                                  dropout_seed=self.dropout_seed)
         self.tune_state = TR.TuneState(self.prototypes)
         # load_gan's epoch and accuracy_list are the ones the plugin keeps (PreGANPlus.py:32-34);
         # the encoder checkpoint's own are kept for an explicit full save

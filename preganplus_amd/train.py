@@ -94,8 +94,17 @@ class Trainer:
     SECTIONS = ("transformer", "gen", "disc")
 
     def __init__(self, H: int, weights: dict, extra: dict | None = None, lrs: dict | None = None,
-                 device="cuda", max_batch: int = 16, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8):
+                 device="cuda", max_batch: int = 16, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8,
+                 dropout: float = 0.0, dropout_seed: int = 0):
         self.H = int(H)
+        # train-mode dropout of the Transformer (models.py:300,311,354; the reference's p is 0.1) in the
+        # fused batch-1 step only (tune_step1 / backprop at 8 / 16 hosts); 0: the deterministic step
+        self.dropout, self.dropout_seed = float(dropout), int(dropout_seed) & (2 ** 64 - 1)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"dropout {dropout} outside [0, 1)")
+        if self.dropout > 0 and self.H not in FUSED_STEP_HOSTS:
+            raise ValueError(f"dropout > 0 runs in the fused batch-1 step only: n_hosts in {FUSED_STEP_HOSTS}, "
+                             f"not {self.H}")
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -136,6 +145,10 @@ class Trainer:
             self.v.copy_(torch.tensor(v))
         self.sec_off = {s: int(L.pgp_master_offset(self.H, i)) for i, s in enumerate(self.SECTIONS)}
         self.sec_end = {"transformer": self.sec_off["gen"], "gen": self.sec_off["disc"], "disc": n}
+        # {seed, base step} of the dropout masks as the step kernel reads them (2 x uint64)
+        self.drop_rng = torch.zeros(2, dtype=torch.int64, device=dev)
+        if self.dropout > 0:
+            self.set_dropout_base(self.dropout_base())
         self._alloc(max_batch)
 
     def _bind(self):
@@ -165,6 +178,11 @@ class Trainer:
                                       + [vp])
         dbl = ctypes.c_double
         L.pgp_tune_step1.argtypes = [i32, i32] + [vp] * 6 + [dbl, dbl] + [vp] * 3 + [vp]
+        L.pgp_tune_step1_dropout.argtypes = ([i32, i32] + [vp] * 6 + [dbl, dbl] + [vp] * 3
+                                             + [ctypes.c_float, vp, i32] + [vp])
+        L.pgp_tune_dropout_masks.argtypes = [i32, ctypes.c_float, vp, i32, vp] + [vp]
+        L.pgp_tune_dropout_mask_len.argtypes = [i32]
+        L.pgp_tune_dropout_mask_len.restype = sz
         L.pgp_forward1.argtypes = [i32, i32] + [vp] * 12 + [vp]
         L.pgp_tune_forward_many.argtypes = [i32, i32] + [vp] * 4 + [vp]
         L.pgp_gan_forward1.argtypes = [i32] + [vp] * 6 + [vp]
@@ -181,7 +199,7 @@ class Trainer:
                   "pgp_gan_gen_backward", "pgp_adamw", "pgp_load_weights_master", "pgp_tune_targets",
                   "pgp_adamw_table", "pgp_tune_dataset", "pgp_tune_targets_dp", "pgp_tune_state_apply",
                   "pgp_gan_probs", "pgp_tune_step1", "pgp_forward1", "pgp_tune_forward_many",
-                  "pgp_gan_forward1", "pgp_gan_step1"):
+                  "pgp_gan_forward1", "pgp_gan_step1", "pgp_tune_step1_dropout", "pgp_tune_dropout_masks"):
             getattr(L, f).restype = i32
         L._pgp_train_bound = True
 
@@ -281,6 +299,8 @@ class Trainer:
         the batch of the preceding tune_forward, or fewer: then the gradient is
         of its FIRST B windows' losses (``pgp_tune_backward_prefix``; the rest
         were inference windows sharing the forward, e.g. C3's detect)."""
+        if self.dropout > 0:
+            raise ValueError("dropout > 0 runs in the fused batch-1 step only (tune_step1), not tune_backward")
         if not 0 < B <= self._fwd_batch:
             raise ValueError(f"tune_backward batch {B} not in 1..{self._fwd_batch} (the tune_forward batch)")
         y = self._dev(y, torch.int32)
@@ -311,18 +331,59 @@ class Trainer:
             state.data_ptr(), PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY, mult.data_ptr(), tgt.data_ptr(),
             loss.data_ptr(), self._stream()), "pgp_tune_targets")
 
-    def tune_step1(self, window, y, cls, state, loss):
+    def dropout_base(self) -> int:
+        """The optimizer step the next backprop() call's first step is: the
+        transformer section's AdamW count of a tensor every step updates
+        (``time_encoder.weight``).  Checkpoints carry it, so a resumed run
+        continues the mask sequence."""
+        for t in self.tensors:
+            if t["section"] == "transformer" and t["name"] == "time_encoder.weight":
+                return int(t["step"])
+        raise KeyError("time_encoder.weight")
+
+    def dropout_rng_words(self, base: int) -> np.ndarray:
+        """{seed, base step} as the two 64-bit words the step kernel reads."""
+        return np.array([self.dropout_seed, int(base) & (2 ** 64 - 1)], dtype=np.uint64).view(np.int64)
+
+    def set_dropout_base(self, base: int):
+        """Upload {dropout_seed, base} to ``drop_rng``, the device words
+        tune_step1 reads by default: step i of a host loop uses the masks of
+        optimizer step base + i."""
+        self.drop_rng.copy_(torch.from_numpy(self.dropout_rng_words(base)))
+
+    def tune_step1(self, window, y, cls, state, loss, step: int = 0, rng=None):
         """tune_forward + tune_targets + tune_backward of ONE window as a single
         launch (``pgp_tune_step1``, n_hosts 8 or 16): window [1,3,3H] (or
         [3,3H]), y, cls [H] int32, state as tune_targets; writes logits /
         protos, loss [2] fp64 and the transformer section of G.  Device
-        tensors."""
+        tensors.  With ``dropout`` > 0 the launch is ``pgp_tune_step1_dropout``
+        with the masks of optimizer step rng[1] + ``step`` under seed rng[0]
+        (``rng``: 2 x 64-bit device words, default ``drop_rng``)."""
         K = (state.numel() - 3) // 2
-        _native.check(self._L.pgp_tune_step1(
-            self.H, K, window.data_ptr(), y.data_ptr(), cls.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
-            state.data_ptr(), PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY, self.logits.data_ptr(),
-            self.protos.data_ptr(), loss.data_ptr(), self._stream()), "pgp_tune_step1")
+        if self.dropout > 0:
+            rng = self.drop_rng if rng is None else rng
+            _native.check(self._L.pgp_tune_step1_dropout(
+                self.H, K, window.data_ptr(), y.data_ptr(), cls.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
+                state.data_ptr(), PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY, self.logits.data_ptr(),
+                self.protos.data_ptr(), loss.data_ptr(), self.dropout, rng.data_ptr(), int(step), self._stream()),
+                "pgp_tune_step1_dropout")
+        else:
+            _native.check(self._L.pgp_tune_step1(
+                self.H, K, window.data_ptr(), y.data_ptr(), cls.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
+                state.data_ptr(), PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY, self.logits.data_ptr(),
+                self.protos.data_ptr(), loss.data_ptr(), self._stream()), "pgp_tune_step1")
         self._fwd_batch = 0   # the fused step keeps no activations for tune_backward
+
+    def dropout_masks(self, step: int = 0, rng=None, p: float | None = None) -> torch.Tensor:
+        """The keep bytes (1 = kept) tune_step1 would use at ``step``
+        (``pgp_tune_dropout_masks``), in site order: a uint8 device tensor of
+        ``pgp_tune_dropout_mask_len`` elements."""
+        rng = self.drop_rng if rng is None else rng
+        keep = torch.empty(int(self._L.pgp_tune_dropout_mask_len(self.H)), dtype=torch.uint8, device=self.device)
+        _native.check(self._L.pgp_tune_dropout_masks(
+            self.H, self.dropout if p is None else float(p), rng.data_ptr(), int(step), keep.data_ptr(),
+            self._stream()), "pgp_tune_dropout_masks")
+        return keep
 
     def tune_forward_many(self, windows, logits64, protos64):
         """n independent batch-1 forwards from the master (``pgp_tune_forward_many``,
@@ -704,6 +765,9 @@ class DPTuner:
     CHUNK = 64   # AdamW table rows precomputed per upload
 
     def __init__(self, tr: "Trainer", st: TuneState, max_batch: int, group=None):
+        if tr.dropout > 0:
+            raise ValueError("dropout > 0 runs in the fused batch-1 step only (backprop at 8 / 16 hosts), "
+                             "not the data-parallel tuner")
         self.tr, self.group = tr, group
         H, dev, L = tr.H, tr.device, tr._L
         self.K = st.protos.shape[0]
@@ -928,13 +992,16 @@ class _TuneGraph:
         H, dev = tr.H, tr.device
         if fused is None:
             fused = H in FUSED_STEP_HOSTS
+        if tr.dropout > 0 and not fused:
+            raise ValueError("dropout > 0 runs in the fused batch-1 step only, not the token-major kernels")
         self.n, self.fused, self.score, self.K = n, fused, score, K
         self.sel = [t for t in tr.tensors if t["section"] == "transformer" and t["trainable"]]
         nw = int(np.prod(win_shape))
-        # input staging: windows f32 | y i32 | cls i32 | AdamW table f32 | state f64 (8-byte aligned)
+        # input staging: windows f32 | y i32 | cls i32 | AdamW table f32 | state f64 | dropout rng
+        # {seed, base step} 2 x u64 (8-byte aligned)
         parts = [("W", torch.float32, (n,) + tuple(win_shape)), ("Y", torch.int32, (n, H)),
                  ("C", torch.int32, (n, H)), ("sched", torch.float32, (n, len(self.sel), 3)),
-                 ("state", torch.float64, (2 * K + 3,))]
+                 ("state", torch.float64, (2 * K + 3,)), ("rng", torch.int64, (2,))]
         off, lay = 0, []
         for name, dt, shp in parts:
             nb = int(np.prod(shp)) * torch.tensor([], dtype=dt).element_size()
@@ -961,7 +1028,7 @@ class _TuneGraph:
         with torch.cuda.graph(self.graph):
             for i in range(n):
                 if fused:
-                    tr.tune_step1(self.W[i], self.Y[i], self.C[i], self.state, self.loss[i])
+                    tr.tune_step1(self.W[i], self.Y[i], self.C[i], self.state, self.loss[i], step=i, rng=self.rng)
                 else:
                     tr.tune_forward(self.W[i:i + 1])
                     tr.tune_targets(self.Y[i], self.C[i], self.state, self.mult, self.tgt, self.loss[i])
@@ -978,10 +1045,12 @@ class _TuneGraph:
                     self.dout[o:o + 2 * n * H].copy_(lg.reshape(-1))
                     self.dout[o + 2 * n * H:o + 4 * n * H].copy_(pr.reshape(-1))
 
-    def launch(self, tr, wins, anom, cls, state_vec, tab, stream=None):
+    def launch(self, tr, wins, anom, cls, state_vec, tab, stream=None, drop_base: int = 0):
         """Upload, replay and download on ``stream`` (default: the current
-        one) without waiting; ``wait()`` returns the gathered outputs."""
+        one) without waiting; ``wait()`` returns the gathered outputs.  Step i
+        of the graph draws the dropout masks of optimizer step drop_base + i."""
         hv = self.hviews
+        hv["rng"][...] = tr.dropout_rng_words(drop_base)
         hv["W"][...] = wins
         hv["Y"][...] = anom
         hv["C"][...] = cls
@@ -1021,6 +1090,11 @@ def backprop(tr: Trainer, st: TuneState, wins, anom, cls, fused: bool | None = N
     ``loss_targets`` is the same bookkeeping in numpy (the tests restate with
     it).
 
+    With ``tr.dropout`` > 0 (8 / 16 hosts, the fused step) step i of the call
+    trains with the dropout masks of optimizer step base + i, base = the
+    trainer's step count before the call (``Trainer.dropout_base``): a call
+    never reuses an earlier call's masks.
+
     With ``defer`` the graph is launched on ``stream`` (default: the current
     one) and a function is returned that waits for it and returns what
     backprop would (the plugin overlaps the tuning graph with train_gan's host
@@ -1039,14 +1113,15 @@ def backprop(tr: Trainer, st: TuneState, wins, anom, cls, fused: bool | None = N
     K = st.protos.shape[0]
     if fused is None:
         fused = H in FUSED_STEP_HOSTS
-    key = (n, wins.shape[1:], K, bool(fused), bool(score))
+    key = (n, wins.shape[1:], K, bool(fused), bool(score), tr.dropout)
     g = tr._graphs.get(key)
     if g is None or g.generation != tr.generation:
         g = _TuneGraph(tr, n, wins.shape[1:], K, fused, score)
         tr._graphs[key] = g
     positive = np.any(anom > 0, axis=1)
+    drop_base = tr.dropout_base()   # before adam_schedule_np advances the counts: masks never repeat across calls
     tab = tr.adam_schedule_np("transformer", positive, ("prototype_decoder.0.weight", "prototype_decoder.0.bias"))
-    g.launch(tr, wins, anom, cls, st.vector(), tab, stream)
+    g.launch(tr, wins, anom, cls, st.vector(), tab, stream, drop_base)
 
     def finish():
         out = g.wait()
@@ -1424,6 +1499,9 @@ class OnlineTrainStep:
 
     def __init__(self, tr: "Trainer", st: "TuneState", sim, series, train_max, sched, envs, R: int = 10,
                  side=None, groups=(None, None), out=None, native: bool = True):
+        if tr.dropout > 0:
+            raise ValueError("dropout > 0 runs in the fused batch-1 step only (backprop at 8 / 16 hosts), "
+                             "not the online training step")
         self.tr, self.sim, self.st = tr, sim, st
         self.series, self.tmax = tr._dev(series, torch.float64), tr._dev(train_max, torch.float64)
         E = self.series.shape[0]
