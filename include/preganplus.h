@@ -41,6 +41,9 @@
  *   pgp_gobi_*
  *       the schedule producer upstream of the path: GOBIScheduler.run_GOBI's
  *       opt() (scheduler/GOBI.py:19-42, scheduler/BaGTI/src/opt.py:17-33)
+ *   pgp_gobi_train_steps / pgp_gobi_train_eval
+ *       the training of GOBI's surrogate: backprop / accuracy of
+ *       scheduler/BaGTI/train.py:18-42 (the epoch loop :81-91 stays in Python)
  *   pgp_sim_env_len / pgp_simulate
  *       the GAN label: run_simulation (PreGANSrc/src/utils.py:97-100) ->
  *       Stats.runSimulation (stats/Stats.py:154-177), PreGANPlus.py:65-66
@@ -656,6 +659,36 @@ const char* pgp_gobi_last_error(void);
  * one-hot projection (a test tap). */
 int pgp_gobi_optimize(pgp_gobi* g, int n_env, const float* init, float* result, int* iterations,
                       float* fitness, int max_iters, float* pre, void* stream);
+
+/* Training of that surrogate (scheduler/BaGTI/train.py:69-94, the reference's
+ * `python train.py energy_latency_16 train`), 16 hosts; any other n_hosts is
+ * PGP_ERR_UNSUPPORTED.  All pointers are device pointers.
+ * P / exp_avg / exp_avg_sq: pgp_gobi_weight_len(H) floats each, the state-dict
+ * order above, updated in place.  feats [N,H,H+2] fp32 (utils.py:57-78 rows,
+ * train.py:22), targets [N,2] fp32, N = n_samples; order [n]: indices into N
+ * (an index outside [0, N) takes no step and gets a NaN loss).
+ * pgp_gobi_train_steps: n sequential batch-1 steps of backprop (train.py:18-31)
+ *   in ONE launch of one workgroup: forward (models.py:8-27, the 2-vector),
+ *   loss sum((y_pred - y_true)^2) (train.py:13-16), backward, and
+ *   torch.optim.Adam with weight_decay as L2 folded into the gradient
+ *   (train.py:53: g += wd p before the moments; NOT pgp_adamw's decoupled
+ *   decay), one step count shared by all tensors: step i of the call is
+ *   optimizer step step0 + i + 1 (its bias corrections are taken from double
+ *   powers in the kernel).  loss [n] fp32, the per-sample loss before the
+ *   step's update.  Fixed summation order, no atomics: the same inputs give
+ *   the same bits, and n launches of one step equal one launch of n.
+ *   PGP_ERR_ARG (before any launch): n < 0, n_samples < 0, lr <= 0, weight_decay < 0, a beta
+ *   outside [0, 1), eps < 0, step0 < 0, a NULL pointer with n > 0.  n == 0
+ *   launches nothing.
+ * pgp_gobi_train_eval: accuracy()'s per-sample loss (train.py:33-42) of the n
+ *   samples order[0..n), one workgroup per sample: loss[i] depends on sample
+ *   order[i] and P alone. */
+int pgp_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
+                         const int* order, float* P, float* exp_avg, float* exp_avg_sq, long long step0,
+                         double lr, double weight_decay, double beta1, double beta2, double eps, float* loss,
+                         void* stream);
+int pgp_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
+                        const int* order, const float* P, float* loss, void* stream);
 
 /* ---- GAN-label simulation ----
  * Replaces the two env.stats.runSimulation calls of train_gan

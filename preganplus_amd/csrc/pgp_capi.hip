@@ -455,6 +455,38 @@ int pgp_fpe_forward_many(int n_hosts, int n, const float* windows, const float* 
   return PGP_OK;
 }
 
+static const char* kGobiTrainHosts = "GOBI surrogate training: only energy_latency_16 exists (16 hosts)";
+
+int pgp_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
+                         const int* order, float* P, float* exp_avg, float* exp_avg_sq, long long step0,
+                         double lr, double weight_decay, double beta1, double beta2, double eps, float* loss,
+                         void* stream) {
+  if (!gobi_train_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, kGobiTrainHosts);
+  if (n < 0 || n_samples < 0 || step0 < 0)
+    return fail(PGP_ERR_ARG, "gobi_train_steps: negative n, n_samples or step0");
+  if (!(lr > 0.0) || !(weight_decay >= 0.0) || !(eps >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+      !(beta2 >= 0.0 && beta2 < 1.0))
+    return fail(PGP_ERR_ARG, "gobi_train_steps: lr > 0, weight_decay >= 0, eps >= 0, betas in [0, 1)");
+  if (n == 0) return PGP_OK;
+  if (!feats || !targets || !order || !P || !exp_avg || !exp_avg_sq || !loss)
+    return fail(PGP_ERR_ARG, "gobi_train_steps: NULL argument");
+  const GobiTrainHyper hy{lr, weight_decay, beta1, beta2, eps};
+  HIPCHK(launch_gobi_train_steps(n_hosts, n_samples, n, feats, targets, order, P, exp_avg, exp_avg_sq, step0, hy,
+                                 loss, reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, const float* targets, const int* order,
+                        const float* P, float* loss, void* stream) {
+  if (!gobi_train_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, kGobiTrainHosts);
+  if (n < 0 || n_samples < 0) return fail(PGP_ERR_ARG, "gobi_train_eval: negative n or n_samples");
+  if (n == 0) return PGP_OK;
+  if (!feats || !targets || !order || !P || !loss) return fail(PGP_ERR_ARG, "gobi_train_eval: NULL argument");
+  HIPCHK(launch_gobi_train_eval(n_hosts, n_samples, n, feats, targets, order, P, loss,
+                                reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
 int pgp_tune_reserve_cus(int n) {
   if (n < 0) return fail(PGP_ERR_ARG, "negative CU count");
   tf_reserve_cus(n);

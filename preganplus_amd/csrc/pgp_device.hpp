@@ -77,6 +77,18 @@ hipError_t launch_fpe_step(int n_hosts, const float* win, const float* h0, const
 hipError_t launch_fpe_forward_many(int n_hosts, int n, const float* wins, const float* h0s, const float* P,
                                    double* probs, double* protos, hipStream_t st);
 
+// training of GOBI's surrogate (pgp_gobitrain.hip), 16 hosts: n sequential batch-1 Adam (L2) steps in
+// one launch / n independent per-sample losses.  hipErrorInvalidValue for any other H.
+struct GobiTrainHyper {
+  double lr, wd, beta1, beta2, eps;
+};
+bool gobi_train_supported(int H);
+hipError_t launch_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
+                                   const int* order, float* P, float* m, float* v, long long step0,
+                                   const GobiTrainHyper& hy, float* loss, hipStream_t st);
+hipError_t launch_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
+                                  const int* order, const float* P, float* loss, hipStream_t st);
+
 // recover_decision's per-container moves (pgp_decide.hip)
 hipError_t launch_decide(int B, int C, const int* keep, const int* target, const int* cur, int* moves,
                          int* hosts_from, hipStream_t st);

@@ -40,6 +40,7 @@ class GOBIOptimizer:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise ValueError("GOBIOptimizer runs on the GPU only (no CPU fallback)")
+        self.max_ips = None   # known for the packaged weights alone; a trained surrogate's comes from its dataset
         if weights is None:
             weights, self.max_ips = load_weights()
         L = _native.lib()
@@ -131,12 +132,18 @@ class GOBIScheduler(Scheduler):
     (hostlist[i].getCPU(), containerlist[c].getApparentIPS() / getHostID() / id),
     a drop-in for the scheduler main.py builds (``GOBIScheduler('energy_latency_16')``)."""
 
-    def __init__(self, data_type="energy_latency_16", device="cuda"):
+    def __init__(self, data_type="energy_latency_16", device="cuda", weights=None, max_ips=None):
+        """weights / max_ips: a surrogate trained on the environment's own
+        traces (gobitrain.GOBITrainer.weights_numpy() and the max_ips of
+        gobitrain.load_energy_latency_data); both or neither.  None: the
+        packaged copy of the reference's checkpoint."""
         super().__init__()
         if data_type != "energy_latency_16":
             raise ValueError("only the energy_latency_16 surrogate ships with the reference")
-        self.opt = GOBIOptimizer(device=device)
-        self.max_container_ips = self.opt.max_ips
+        if (weights is None) != (max_ips is None):
+            raise ValueError("a trained surrogate comes with its dataset's max_ips: pass weights and max_ips together")
+        self.opt = GOBIOptimizer(weights=weights, device=device)
+        self.max_container_ips = self.opt.max_ips if max_ips is None else float(max_ips)
         self.data_type = data_type
         self.hosts = H
         self.result_cache = None
