@@ -44,6 +44,11 @@
  *   pgp_gobi_train_steps / pgp_gobi_train_eval
  *       the training of GOBI's surrogate: backprop / accuracy of
  *       scheduler/BaGTI/train.py:18-42 (the epoch loop :81-91 stays in Python)
+ *   pgp_gobi_train_steps_many / pgp_gobi_train_eval_many / pgp_gobi_create_many /
+ *   pgp_gobi_set_model / pgp_gobi_optimize_groups / pgp_gobi_plan_groups
+ *       a fleet whose environments have their own surrogates (one dataset and
+ *       checkpoint per environment, scheduler/GOBI.py:11-17): M trained in one
+ *       launch, each environment optimised against its own
  *   pgp_sim_env_len / pgp_simulate
  *       the GAN label: run_simulation (PreGANSrc/src/utils.py:97-100) ->
  *       Stats.runSimulation (stats/Stats.py:154-177), PreGANPlus.py:65-66
@@ -689,6 +694,92 @@ int pgp_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, 
                          void* stream);
 int pgp_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
                         const int* order, const float* P, float* loss, void* stream);
+
+/* ---- A fleet of surrogates ----
+ * The reference keeps one surrogate per environment: one dataset and one
+ * checkpoint per data_type under scheduler/BaGTI/, loaded by
+ * GOBIScheduler.__init__ (scheduler/GOBI.py:11-17).  These entries train
+ * n_models of them in one launch and optimise each environment against its own.
+ * 16 hosts only (PGP_ERR_UNSUPPORTED otherwise).
+ *
+ * One job per model.  Job m owns slot m of P / exp_avg / exp_avg_sq
+ * ([n_models][pgp_gobi_weight_len(16)] floats, contiguous), so two jobs cannot
+ * alias a model.  feats [n_pool_samples,16,18] and targets [n_pool_samples,2]
+ * are a pool; job m reads n_samples of them from sample_off (jobs may share a
+ * range: a seed or learning-rate sweep over one dataset).  order (int32) and
+ * loss (fp32) are pools of n_pool_steps entries; job m's n entries start at
+ * order_off, and its order indices are relative to sample_off. */
+typedef struct pgp_gobi_job {
+  long long sample_off, order_off; /* first sample / first order and loss entry of the job */
+  long long step0;                 /* optimizer steps already taken (pgp_gobi_train_steps's step0) */
+  int n_samples, n;                /* the job's dataset size; its steps (eval: samples to score) */
+  double lr, weight_decay, beta1, beta2, eps; /* torch.optim.Adam's, train.py:53; doubles as the single entry's */
+} pgp_gobi_job;
+/* pgp_gobi_train_steps_many: backprop (scheduler/BaGTI/train.py:18-31) of every
+ *   job, one workgroup per model running pgp_gobi_train_steps's step loop on
+ *   its own slot, data and scalars: model m's P, moments and losses have the
+ *   bits of the single entry called with job m's arguments.  Ragged: every field
+ *   is per job; n == 0 leaves the slot untouched; an order entry outside
+ *   [0, n_samples) takes no step and gets a NaN loss.  n_models is not limited
+ *   by the device (workgroups queue); no workgroup waits for another.
+ *   jobs: host array [n_models].  jobs_dev: device scratch of n_models *
+ *   sizeof(pgp_gobi_job) bytes that the library fills on `stream` before the
+ *   launch (the descriptors reach the kernel through memory, so one launch
+ *   holds any number of models); like any asynchronous copy, `jobs` must stay
+ *   unchanged until the stream has passed the call, and jobs_dev until the
+ *   kernel has ended.
+ *   PGP_ERR_ARG before anything is enqueued, all or nothing: n_models or a
+ *   pool size < 0; in any job the single entry's rules (n, n_samples, step0 <
+ *   0, lr <= 0, weight_decay < 0, eps < 0, a beta outside [0, 1)), sample_off or
+ *   order_off < 0, sample_off + n_samples > n_pool_samples, order_off + n >
+ *   n_pool_steps; a NULL pointer while some job has n > 0.  n_models == 0 or no
+ *   job with n > 0: PGP_OK, nothing launched.
+ * pgp_gobi_train_eval_many: accuracy()'s per-sample loss (train.py:33-42) for
+ *   each model: one workgroup per (job, sample) pair, loss[order_off + i] from
+ *   sample order[order_off + i] of the job's range and slot m alone (the same
+ *   bits in whatever launch it is computed).  Reads n_samples, n and the two
+ *   offsets of a job; the same range rules. */
+int pgp_gobi_train_steps_many(int n_hosts, int n_models, const pgp_gobi_job* jobs, long long n_pool_samples,
+                              const float* feats, const float* targets, long long n_pool_steps, const int* order,
+                              float* P, float* exp_avg, float* exp_avg_sq, float* loss, void* jobs_dev,
+                              void* stream);
+int pgp_gobi_train_eval_many(int n_hosts, int n_models, const pgp_gobi_job* jobs, long long n_pool_samples,
+                             const float* feats, const float* targets, long long n_pool_steps, const int* order,
+                             const float* P, float* loss, void* jobs_dev, void* stream);
+
+/* pgp_gobi_create_many: a handle of n_models (>= 1) surrogates; weights is
+ *   [n_models][pgp_gobi_weight_len(16)] host floats (len = the whole array's),
+ *   each packed as pgp_gobi_create packs one.  pgp_gobi_optimize on it runs
+ *   every environment on model 0, so a one-model handle is pgp_gobi_create's.
+ * pgp_gobi_model_count: its number of models (a pgp_gobi_create handle: 1; NULL: 0).
+ * pgp_gobi_set_model: repack slot m (a cell whose surrogate was retrained; what
+ *   GOBIScheduler.__init__, GOBI.py:11-17, does when it loads another
+ *   checkpoint).  A blocking copy, ordered like pgp_gobi_create's upload: call
+ *   it when no optimise using the handle is in flight.
+ * pgp_gobi_optimize_groups: opt() (scheduler/BaGTI/src/opt.py:17-33) of each
+ *   environment against its own surrogate.  groups: device int32 [n_groups][5]
+ *   = {model, env0, env1, env2, env3}, -1 for an empty slot.  Workgroup b loads
+ *   model groups[b][0] and runs the listed environments, indexing init /
+ *   result / iterations / fitness / pre by environment id, so those arrays
+ *   stay in the caller's order and have pgp_gobi_optimize's shapes.  An
+ *   environment's result has the bits pgp_gobi_optimize gives it on a handle
+ *   of its model alone.  A model outside [0, models), an environment outside
+ *   [0, n_env) or one that repeats an earlier slot of its group is inert:
+ *   nothing is read or written for it.  An environment no group names keeps
+ *   its output rows as they were; one named by two groups is the caller's error
+ *   (both write its rows; nothing outside the arrays is touched).
+ * pgp_gobi_plan_groups: a pure host function: model_of_env [n_env] -> the
+ *   table, groups in ascending model order, environments in ascending id within
+ *   a model, four per group, the last group of a model padded with -1.  Returns
+ *   the number of groups (groups_out holds cap groups), or PGP_ERR_ARG for a
+ *   model index outside [0, n_models), a negative n_env or a cap too small. */
+int pgp_gobi_create_many(int n_hosts, int n_models, const float* weights, size_t len, pgp_gobi** out);
+int pgp_gobi_model_count(const pgp_gobi* g);
+int pgp_gobi_set_model(pgp_gobi* g, int m, const float* weights, size_t len);
+int pgp_gobi_optimize_groups(pgp_gobi* g, int n_env, int n_groups, const int* groups, const float* init,
+                             float* result, int* iterations, float* fitness, int max_iters, float* pre,
+                             void* stream);
+int pgp_gobi_plan_groups(int n_env, const int* model_of_env, int n_models, int* groups_out, int cap);
 
 /* ---- GAN-label simulation ----
  * Replaces the two env.stats.runSimulation calls of train_gan

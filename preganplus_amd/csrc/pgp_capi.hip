@@ -487,6 +487,72 @@ int pgp_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, c
   return PGP_OK;
 }
 
+namespace {
+// the many-entries' checks of the whole job table; work = some job has n > 0, max_n = the longest job
+int gobi_jobs_check(const char* who, bool steps, int n_hosts, int n_models, const pgp_gobi_job* jobs,
+                    long long n_pool_samples, long long n_pool_steps, bool* work, int* max_n) {
+  const std::string w(who);
+  *work = false;
+  *max_n = 0;
+  if (!gobi_train_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, kGobiTrainHosts);
+  if (n_models < 0 || n_pool_samples < 0 || n_pool_steps < 0)
+    return fail(PGP_ERR_ARG, w + ": negative n_models or pool size");
+  if (n_models == 0) return PGP_OK;
+  if (!jobs) return fail(PGP_ERR_ARG, w + ": NULL jobs");
+  for (int m = 0; m < n_models; ++m) {
+    const pgp_gobi_job& j = jobs[m];
+    const std::string at = w + ": job " + std::to_string(m) + ": ";
+    if (j.n < 0 || j.n_samples < 0 || (steps && j.step0 < 0))
+      return fail(PGP_ERR_ARG, at + "negative n, n_samples or step0");
+    if (steps && (!(j.lr > 0.0) || !(j.weight_decay >= 0.0) || !(j.eps >= 0.0) ||
+                  !(j.beta1 >= 0.0 && j.beta1 < 1.0) || !(j.beta2 >= 0.0 && j.beta2 < 1.0)))
+      return fail(PGP_ERR_ARG, at + "lr > 0, weight_decay >= 0, eps >= 0, betas in [0, 1)");
+    if (j.sample_off < 0 || j.sample_off > n_pool_samples || j.n_samples > n_pool_samples - j.sample_off)
+      return fail(PGP_ERR_ARG, at + "sample range outside the pool");
+    if (j.order_off < 0 || j.order_off > n_pool_steps || j.n > n_pool_steps - j.order_off)
+      return fail(PGP_ERR_ARG, at + "order / loss range outside the pool");
+    if (j.n > 0) *work = true;
+    if (j.n > *max_n) *max_n = j.n;
+  }
+  return PGP_OK;
+}
+}  // namespace
+
+int pgp_gobi_train_steps_many(int n_hosts, int n_models, const pgp_gobi_job* jobs, long long n_pool_samples,
+                              const float* feats, const float* targets, long long n_pool_steps, const int* order,
+                              float* P, float* exp_avg, float* exp_avg_sq, float* loss, void* jobs_dev,
+                              void* stream) {
+  bool work;
+  int max_n;
+  const int rc = gobi_jobs_check("gobi_train_steps_many", true, n_hosts, n_models, jobs, n_pool_samples,
+                                 n_pool_steps, &work, &max_n);
+  if (rc != PGP_OK || !work) return rc;
+  if (!feats || !targets || !order || !P || !exp_avg || !exp_avg_sq || !loss || !jobs_dev)
+    return fail(PGP_ERR_ARG, "gobi_train_steps_many: NULL argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipMemcpyAsync(jobs_dev, jobs, (size_t)n_models * sizeof(pgp_gobi_job), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_gobi_train_steps_many(n_hosts, n_models, static_cast<const pgp_gobi_job*>(jobs_dev), feats, targets,
+                                      order, P, exp_avg, exp_avg_sq, loss, st));
+  return PGP_OK;
+}
+
+int pgp_gobi_train_eval_many(int n_hosts, int n_models, const pgp_gobi_job* jobs, long long n_pool_samples,
+                             const float* feats, const float* targets, long long n_pool_steps, const int* order,
+                             const float* P, float* loss, void* jobs_dev, void* stream) {
+  bool work;
+  int max_n;
+  const int rc = gobi_jobs_check("gobi_train_eval_many", false, n_hosts, n_models, jobs, n_pool_samples,
+                                 n_pool_steps, &work, &max_n);
+  if (rc != PGP_OK || !work) return rc;
+  if (!feats || !targets || !order || !P || !loss || !jobs_dev)
+    return fail(PGP_ERR_ARG, "gobi_train_eval_many: NULL argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipMemcpyAsync(jobs_dev, jobs, (size_t)n_models * sizeof(pgp_gobi_job), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_gobi_train_eval_many(n_hosts, n_models, max_n, static_cast<const pgp_gobi_job*>(jobs_dev), feats,
+                                     targets, order, P, loss, st));
+  return PGP_OK;
+}
+
 int pgp_tune_reserve_cus(int n) {
   if (n < 0) return fail(PGP_ERR_ARG, "negative CU count");
   tf_reserve_cus(n);

@@ -8,6 +8,8 @@
 
 #include "pgp_layout.hpp"
 
+struct pgp_gobi_job;  // include/preganplus.h
+
 namespace pgp {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -88,6 +90,14 @@ hipError_t launch_gobi_train_steps(int n_hosts, int n_samples, int n, const floa
                                    const GobiTrainHyper& hy, float* loss, hipStream_t st);
 hipError_t launch_gobi_train_eval(int n_hosts, int n_samples, int n, const float* feats, const float* targets,
                                   const int* order, const float* P, float* loss, hipStream_t st);
+// n_models surrogates at once: jobs_dev [n_models] on the device (already validated), slot m of P / m / v for
+// job m; one workgroup per model / per (sample, model) pair with max_n the longest job
+hipError_t launch_gobi_train_steps_many(int n_hosts, int n_models, const pgp_gobi_job* jobs_dev, const float* feats,
+                                        const float* targets, const int* order, float* P, float* m, float* v,
+                                        float* loss, hipStream_t st);
+hipError_t launch_gobi_train_eval_many(int n_hosts, int n_models, int max_n, const pgp_gobi_job* jobs_dev,
+                                       const float* feats, const float* targets, const int* order, const float* P,
+                                       float* loss, hipStream_t st);
 
 // recover_decision's per-container moves (pgp_decide.hip)
 hipError_t launch_decide(int B, int C, const int* keep, const int* target, const int* cur, int* moves,

@@ -21,8 +21,13 @@
 // x - tanh x composite, sigmoid backward g(1-y)y, AdamW single-tensor op
 // order); per-iteration AdamW scalars (cosine lr) are computed on the host in
 // double, as torch does.
+//
+// gobi_groups_kernel is the same optimisation with one surrogate per
+// workgroup, picked by a group table (a fleet whose environments have their
+// own surrogates, scheduler/GOBI.py:11-17): see gobi_run<GROUPED>.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -476,12 +481,39 @@ __device__ void surrogate_fwd(const float* __restrict__ W, const GobiRegs& R, Go
   GMARK(3);
 }
 
-__global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict__ W, const float* __restrict__ init,
-                                                  float* __restrict__ result, int* __restrict__ iterations,
-                                                  float* __restrict__ fitness, int max_it, float* __restrict__ pre) {
+// The whole optimisation of a workgroup's kNE environments on the surrogate W.
+// GROUPED = false (gobi_kernel): environments e0 .. e0 + 3 of the batch, e0 =
+// 4 blockIdx.x.  GROUPED = true (gobi_groups_kernel): the environments env[0..3]
+// of a group table's row (wave-uniform; < 0: the slot is empty), every array
+// indexed by environment id.  Everything else is the same code, and the
+// ungrouped instantiation is the kernel as it was.
+template <bool GROUPED>
+__device__ __forceinline__ void gobi_run(GobiLds& L, int E, const float* __restrict__ W,
+                                         const float* __restrict__ init, float* __restrict__ result,
+                                         int* __restrict__ iterations, float* __restrict__ fitness, int max_it,
+                                         float* __restrict__ pre, const int (&env)[kNE]) {
 #pragma clang fp contract(off)  // elementwise steps as torch's separate mul/add
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  GobiLds& L = *reinterpret_cast<GobiLds*>(lds_raw);
+  // slot e holds an environment / its id (a select chain: no dynamic index into the uniform ids)
+  auto live = [&](int e) -> bool {
+    if constexpr (GROUPED) {
+      int id = env[0];
+#pragma unroll
+      for (int q = 1; q < kNE; ++q) id = e == q ? env[q] : id;
+      return id >= 0;
+    } else {
+      return (long)blockIdx.x * kNE + e < E;
+    }
+  };
+  auto envid = [&](int e) -> long {
+    if constexpr (GROUPED) {
+      int id = env[0];
+#pragma unroll
+      for (int q = 1; q < kNE; ++q) id = e == q ? env[q] : id;
+      return id;
+    } else {
+      return (long)blockIdx.x * kNE + e;
+    }
+  };
   unsigned long long gmark_t_ = 0;
 #ifdef PGP_GOBI_PROF
   gmark_t_ = wall_clock64();
@@ -496,7 +528,10 @@ __global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict
   }
   for (int k = t; k < kNE * kIn; k += kT) {
     const int e = k / kIn;
-    L.x[e][k - e * kIn] = e0 + e < E ? init[e0 * kIn + k] : 0.f;
+    if constexpr (GROUPED)
+      L.x[e][k - e * kIn] = live(e) ? init[envid(e) * kIn + (k - e * kIn)] : 0.f;
+    else
+      L.x[e][k - e * kIn] = e0 + e < E ? init[e0 * kIn + k] : 0.f;
   }
   for (int k = t; k < kMaxIt * 4; k += kT) (&L.adam[0][0])[k] = W[GobiW::ADAM + k];
   if (t < kNE) {
@@ -539,7 +574,10 @@ __global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict
   int equal[kNE], its[kNE];
 #pragma unroll
   for (int e = 0; e < kNE; ++e) {
-    act[e] = e0 + e < E;
+    if constexpr (GROUPED)
+      act[e] = env[e] >= 0;
+    else
+      act[e] = e0 + e < E;
     dense[e] = __builtin_amdgcn_readfirstlane(L.dense[e]) != 0;
     equal[e] = 0;
     its[e] = max_it;
@@ -629,7 +667,12 @@ __global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict
       take(dppf<kDppRor4>(best), dppi<kDppRor4>(bi));
       take(dppf<kDppRor8>(best), dppi<kDppRor8>(bi));
       if (on) {
-        if (pre) pre[(e0 + e) * kH * kH + entry] = xv;  // test tap: the step's values before the projection
+        // test tap: the step's values before the projection
+        if constexpr (GROUPED) {
+          if (pre) pre[envid(e) * kH * kH + entry] = xv;
+        } else {
+          if (pre) pre[(e0 + e) * kH * kH + entry] = xv;
+        }
         const float nv = bi == hcol ? 1.f : 0.f;
         if (nv != xold) L.flag[it & 1][e] = 1;  // benign race: every writer stores 1
         L.x[e][xi] = nv;
@@ -662,18 +705,27 @@ __global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict
   }
   // final fitness of every real environment
 #pragma unroll
-  for (int e = 0; e < kNE; ++e) act[e] = e0 + e < E;
+  for (int e = 0; e < kNE; ++e) {
+    if constexpr (GROUPED)
+      act[e] = env[e] >= 0;
+    else
+      act[e] = e0 + e < E;
+  }
   surrogate_fwd(W, R, L, K, false, act, dense, gmark_t_);
   for (int k = t; k < kNE * kIn; k += kT) {
     const int e = k / kIn;
-    if (e0 + e < E) result[e0 * kIn + k] = L.x[e][k - e * kIn];
+    if constexpr (GROUPED) {
+      if (live(e)) result[envid(e) * kIn + (k - e * kIn)] = L.x[e][k - e * kIn];
+    } else {
+      if (e0 + e < E) result[e0 * kIn + k] = L.x[e][k - e * kIn];
+    }
   }
-  if (t < kNE && e0 + t < E) {
+  if (t < kNE && live(t)) {
     int n = its[0];
 #pragma unroll
     for (int e = 1; e < kNE; ++e) n = t == e ? its[e] : n;  // no dynamic register-array index
-    iterations[e0 + t] = n;
-    fitness[e0 + t] = L.o[t][2];
+    iterations[envid(t)] = n;
+    fitness[envid(t)] = L.o[t][2];
   }
 #ifdef PGP_GOBI_PROF
   if (blockIdx.x < kProfWG && t == 0) {
@@ -683,6 +735,45 @@ __global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict
 #endif
 }
 
+__global__ __launch_bounds__(kT) void gobi_kernel(int E, const float* __restrict__ W, const float* __restrict__ init,
+                                                  float* __restrict__ result, int* __restrict__ iterations,
+                                                  float* __restrict__ fitness, int max_it, float* __restrict__ pre) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  GobiLds& L = *reinterpret_cast<GobiLds*>(lds_raw);
+  const int none[kNE] = {-1, -1, -1, -1};
+  gobi_run<false>(L, E, W, init, result, iterations, fitness, max_it, pre, none);
+}
+
+// One surrogate per group of up to kNE environments: workgroup b takes row b of
+// groups ([n_groups][1 + kNE] int32: model, then environment ids, -1 = empty),
+// loads model groups[b][0] of the M packed ones at W (GobiW::SIZE floats each)
+// and runs the row's environments.  A table entry never becomes an address
+// unchecked: a model outside [0, M) ends the workgroup before it reads
+// anything else, and an environment outside [0, E) or equal to an earlier slot
+// of its row is an empty slot.
+__global__ __launch_bounds__(kT) void gobi_groups_kernel(int E, int M, const int* __restrict__ groups,
+                                                         const float* __restrict__ W,
+                                                         const float* __restrict__ init, float* __restrict__ result,
+                                                         int* __restrict__ iterations, float* __restrict__ fitness,
+                                                         int max_it, float* __restrict__ pre) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  GobiLds& L = *reinterpret_cast<GobiLds*>(lds_raw);
+  const int* row = groups + (size_t)blockIdx.x * (1 + kNE);
+  const int model = row[0];
+  if (model < 0 || model >= M) return;  // uniform: the whole workgroup
+  int env[kNE];
+#pragma unroll
+  for (int e = 0; e < kNE; ++e) {
+    int id = row[1 + e];
+    if (id < 0 || id >= E) id = -1;
+#pragma unroll
+    for (int q = 0; q < e; ++q)
+      if (id == env[q]) id = -1;
+    env[e] = id;
+  }
+  gobi_run<true>(L, E, W + (size_t)model * GobiW::SIZE, init, result, iterations, fitness, max_it, pre, env);
+}
+
 }  // namespace
 }  // namespace pgp
 
@@ -690,7 +781,8 @@ using namespace pgp;
 
 struct pgp_gobi {
   int H = 0;
-  float* d_w = nullptr;
+  int M = 0;              // surrogates in d_w
+  float* d_w = nullptr;   // [M][GobiW::SIZE]
 };
 
 namespace {
@@ -699,20 +791,9 @@ int gfail(int code, const std::string& msg) {
   g_gerr = msg;
   return code;
 }
-}  // namespace
 
-extern "C" {
-
-size_t pgp_gobi_weight_len(int n_hosts) {
-  if (n_hosts != kH) return 0;
-  return (size_t)kN1 * kIn + kN1 + kN2 * kN1 + kN2 + kN3 * kN2 + kN3 + 2 * kN3 + 2;
-}
-
-int pgp_gobi_create(int n_hosts, const float* weights, size_t len, pgp_gobi** out) {
-  if (!out) return gfail(PGP_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  if (n_hosts != kH) return gfail(PGP_ERR_UNSUPPORTED, "GOBI surrogate: only energy_latency_16 exists (16 hosts)");
-  if (!weights || len != pgp_gobi_weight_len(n_hosts)) return gfail(PGP_ERR_ARG, "GOBI weight length mismatch");
+// one surrogate's device image (GobiW) from its state dict
+void gobi_pack(const float* weights, float* h) {
   // state-dict order: find.0.weight [128,288], find.0.bias, find.2.weight [128,128], find.2.bias,
   //                   find.4.weight [64,128], find.4.bias, find.6.weight [2,64], find.6.bias
   const float* w1 = weights;
@@ -723,7 +804,7 @@ int pgp_gobi_create(int n_hosts, const float* weights, size_t len, pgp_gobi** ou
   const float* b3 = w3 + kN3 * kN2;
   const float* w4 = b3 + kN3;
   const float* b4 = w4 + 2 * kN3;
-  std::vector<float> h(GobiW::SIZE, 0.f);
+  for (int k = 0; k < GobiW::SIZE; ++k) h[k] = 0.f;
   for (int o = 0; o < kN1; ++o)
     for (int k = 0; k < kIn; ++k) {
       h[GobiW::W1 + o * kIn + k] = w1[o * kIn + k];
@@ -761,10 +842,34 @@ int pgp_gobi_create(int n_hosts, const float* weights, size_t len, pgp_gobi** ou
     else
       lr = (1 + std::cos(M_PI * ep / T)) / (1 + std::cos(M_PI * (ep - 1) / T)) * lr;
   }
+}
+
+constexpr const char* kGobiHosts = "GOBI surrogate: only energy_latency_16 exists (16 hosts)";
+}  // namespace
+
+extern "C" {
+
+size_t pgp_gobi_weight_len(int n_hosts) {
+  if (n_hosts != kH) return 0;
+  return (size_t)kN1 * kIn + kN1 + kN2 * kN1 + kN2 + kN3 * kN2 + kN3 + 2 * kN3 + 2;
+}
+
+int pgp_gobi_create_many(int n_hosts, int n_models, const float* weights, size_t len, pgp_gobi** out) {
+  if (!out) return gfail(PGP_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (n_hosts != kH) return gfail(PGP_ERR_UNSUPPORTED, kGobiHosts);
+  if (n_models < 1) return gfail(PGP_ERR_ARG, "GOBI: at least one model");
+  const size_t wl = pgp_gobi_weight_len(n_hosts);
+  if (!weights || len != wl * (size_t)n_models) return gfail(PGP_ERR_ARG, "GOBI weight length mismatch");
+  std::vector<float> h((size_t)GobiW::SIZE * n_models);
+  for (int m = 0; m < n_models; ++m) gobi_pack(weights + wl * m, h.data() + (size_t)GobiW::SIZE * m);
   pgp_gobi* g = new pgp_gobi();
   g->H = n_hosts;
+  g->M = n_models;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gobi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sizeof(GobiLds)) != hipSuccess) {
+                          (int)sizeof(GobiLds)) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&gobi_groups_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GobiLds)) != hipSuccess) {
     delete g;
     return gfail(PGP_ERR_HIP, "GOBI: cannot reserve LDS");
   }
@@ -776,6 +881,49 @@ int pgp_gobi_create(int n_hosts, const float* weights, size_t len, pgp_gobi** ou
   }
   *out = g;
   return PGP_OK;
+}
+
+int pgp_gobi_create(int n_hosts, const float* weights, size_t len, pgp_gobi** out) {
+  return pgp_gobi_create_many(n_hosts, 1, weights, len, out);
+}
+
+int pgp_gobi_model_count(const pgp_gobi* g) { return g ? g->M : 0; }
+
+int pgp_gobi_set_model(pgp_gobi* g, int m, const float* weights, size_t len) {
+  if (!g) return gfail(PGP_ERR_ARG, "NULL optimiser");
+  if (m < 0 || m >= g->M) return gfail(PGP_ERR_ARG, "GOBI: model index outside the handle");
+  if (!weights || len != pgp_gobi_weight_len(g->H)) return gfail(PGP_ERR_ARG, "GOBI weight length mismatch");
+  std::vector<float> h(GobiW::SIZE);
+  gobi_pack(weights, h.data());
+  if (hipMemcpy(g->d_w + (size_t)GobiW::SIZE * m, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) !=
+      hipSuccess)
+    return gfail(PGP_ERR_HIP, "GOBI weight upload failed");
+  return PGP_OK;
+}
+
+int pgp_gobi_plan_groups(int n_env, const int* model_of_env, int n_models, int* groups_out, int cap) {
+  if (n_env < 0 || n_models < 0 || cap < 0) return gfail(PGP_ERR_ARG, "plan_groups: negative count");
+  if (n_env == 0) return 0;
+  if (!model_of_env) return gfail(PGP_ERR_ARG, "plan_groups: NULL model_of_env");
+  std::vector<long> count(n_models, 0), first(n_models + 1, 0);
+  for (int e = 0; e < n_env; ++e) {
+    if (model_of_env[e] < 0 || model_of_env[e] >= n_models)
+      return gfail(PGP_ERR_ARG, "plan_groups: model index outside [0, n_models)");
+    ++count[model_of_env[e]];
+  }
+  for (int m = 0; m < n_models; ++m) first[m + 1] = first[m] + (count[m] + kNE - 1) / kNE;  // groups before model m
+  const long n_groups = first[n_models];
+  if (n_groups > cap || !groups_out) return gfail(PGP_ERR_ARG, "plan_groups: cap too small for the groups");
+  for (long k = 0; k < n_groups * (1 + kNE); ++k) groups_out[k] = -1;
+  std::fill(count.begin(), count.end(), 0);
+  for (int e = 0; e < n_env; ++e) {  // ascending id within each model
+    const int m = model_of_env[e];
+    const long g = first[m] + count[m] / kNE, slot = count[m] % kNE;
+    groups_out[g * (1 + kNE)] = m;
+    groups_out[g * (1 + kNE) + 1 + slot] = e;
+    ++count[m];
+  }
+  return (int)n_groups;
 }
 
 int pgp_gobi_destroy(pgp_gobi* g) {
@@ -808,6 +956,22 @@ int pgp_gobi_optimize(pgp_gobi* g, int n_env, const float* init, float* result, 
                                                                                           iterations, fitness, mi, pre);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return gfail(PGP_ERR_HIP, std::string("gobi_kernel: ") + hipGetErrorString(e));
+  return PGP_OK;
+}
+
+int pgp_gobi_optimize_groups(pgp_gobi* g, int n_env, int n_groups, const int* groups, const float* init,
+                             float* result, int* iterations, float* fitness, int max_iters, float* pre,
+                             void* stream) {
+  if (!g) return gfail(PGP_ERR_ARG, "NULL optimiser");
+  if (n_env < 0 || n_groups < 0) return gfail(PGP_ERR_ARG, "negative batch or group count");
+  if (n_env == 0 || n_groups == 0) return PGP_OK;
+  if (!groups || !init || !result || !iterations || !fitness)
+    return gfail(PGP_ERR_ARG, "NULL table or input/output pointer");
+  const int mi = (max_iters <= 0 || max_iters > kMaxIt) ? kMaxIt : max_iters;
+  gobi_groups_kernel<<<n_groups, kT, sizeof(GobiLds), reinterpret_cast<hipStream_t>(stream)>>>(
+      n_env, g->M, groups, g->d_w, init, result, iterations, fitness, mi, pre);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return gfail(PGP_ERR_HIP, std::string("gobi_groups_kernel: ") + hipGetErrorString(e));
   return PGP_OK;
 }
 

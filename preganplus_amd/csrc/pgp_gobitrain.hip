@@ -34,6 +34,13 @@
 //
 // gobi_train_eval_kernel: accuracy()'s per-sample loss (train.py:33-42), one
 // workgroup per sample, the same forward.
+//
+// gobi_train_steps_many_kernel / gobi_train_eval_many_kernel: the same step
+// loop / loss for M surrogates in one launch (the reference keeps one dataset
+// and checkpoint per environment, scheduler/GOBI.py:11-17): one workgroup per
+// model / per (sample, model) pair, each on its own slot of P, m, v and its own
+// job (pgp_gobi_job, read from a device table).  The workgroups share nothing
+// they write, so a model's bits are those of the single kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -229,14 +236,14 @@ __device__ __forceinline__ void gt_adam_span(float* P, float* M, float* V, const
   }
 }
 
+// the step loop of one surrogate: all kGtT threads of the workgroup, n steps on
+// P / M / V over the samples order[0..n) of feats / targets [N]
 template <int H>
-__global__ __launch_bounds__(kGtT) void gobi_train_steps_kernel(int N, int n, const float* __restrict__ feats,
-                                                                const float* __restrict__ targets,
-                                                                const int* __restrict__ order, float* P, float* M,
-                                                                float* V, long long step0, GobiTrainHyper hy,
-                                                                float* __restrict__ loss) {
+__device__ __forceinline__ void gt_steps(GtLds<H>& L, int N, int n, const float* __restrict__ feats,
+                                         const float* __restrict__ targets, const int* __restrict__ order, float* P,
+                                         float* M, float* V, long long step0, const GobiTrainHyper& hy,
+                                         float* __restrict__ loss) {
   using G = GtGeo<H>;
-  __shared__ GtLds<H> L;
   const int tid = threadIdx.x;
   GtAdam A;
   A.wd = (float)hy.wd;
@@ -335,14 +342,42 @@ __global__ __launch_bounds__(kGtT) void gobi_train_steps_kernel(int N, int n, co
 }
 
 template <int H>
-__global__ __launch_bounds__(kGtT) void gobi_train_eval_kernel(int N, const float* __restrict__ feats,
-                                                               const float* __restrict__ targets,
-                                                               const int* __restrict__ order,
-                                                               const float* __restrict__ P,
-                                                               float* __restrict__ loss) {
+__global__ __launch_bounds__(kGtT) void gobi_train_steps_kernel(int N, int n, const float* __restrict__ feats,
+                                                                const float* __restrict__ targets,
+                                                                const int* __restrict__ order, float* P, float* M,
+                                                                float* V, long long step0, GobiTrainHyper hy,
+                                                                float* __restrict__ loss) {
+  __shared__ GtLds<H> L;
+  gt_steps<H>(L, N, n, feats, targets, order, P, M, V, step0, hy, loss);
+}
+
+// M surrogates in one launch: workgroup b runs job b's step loop on slot b of
+// P / M / V (GtGeo::SIZE floats apart), its own sample range of the pools and
+// its own scalars.  The workgroups share nothing they write, so there is no
+// synchronisation between them and any number of them may queue.
+template <int H>
+__global__ __launch_bounds__(kGtT) void gobi_train_steps_many_kernel(const pgp_gobi_job* __restrict__ jobs,
+                                                                     const float* __restrict__ feats,
+                                                                     const float* __restrict__ targets,
+                                                                     const int* __restrict__ order, float* P, float* M,
+                                                                     float* V, float* __restrict__ loss) {
   using G = GtGeo<H>;
   __shared__ GtLds<H> L;
-  const int t = threadIdx.x, i = blockIdx.x;
+  const pgp_gobi_job j = jobs[blockIdx.x];
+  if (j.n <= 0) return;
+  const GobiTrainHyper hy{j.lr, j.weight_decay, j.beta1, j.beta2, j.eps};
+  const size_t slot = (size_t)blockIdx.x * G::SIZE;
+  gt_steps<H>(L, j.n_samples, j.n, feats + j.sample_off * G::IN, targets + j.sample_off * 2, order + j.order_off,
+              P + slot, M + slot, V + slot, j.step0, hy, loss + j.order_off);
+}
+
+// accuracy()'s loss of sample order[i] under P into loss[i] (all kGtT threads)
+template <int H>
+__device__ __forceinline__ void gt_eval(GtLds<H>& L, int N, int i, const float* __restrict__ feats,
+                                        const float* __restrict__ targets, const int* __restrict__ order,
+                                        const float* __restrict__ P, float* __restrict__ loss) {
+  using G = GtGeo<H>;
+  const int t = threadIdx.x;
   const int s = order[i];
   if (s < 0 || s >= N) {
     if (t == 0) loss[i] = __builtin_nanf("");
@@ -356,6 +391,34 @@ __global__ __launch_bounds__(kGtT) void gobi_train_eval_kernel(int N, const floa
     const float e0 = y0 - targets[2 * (long)s], e1 = y1 - targets[2 * (long)s + 1];
     loss[i] = e0 * e0 + e1 * e1;
   }
+}
+
+template <int H>
+__global__ __launch_bounds__(kGtT) void gobi_train_eval_kernel(int N, const float* __restrict__ feats,
+                                                               const float* __restrict__ targets,
+                                                               const int* __restrict__ order,
+                                                               const float* __restrict__ P,
+                                                               float* __restrict__ loss) {
+  __shared__ GtLds<H> L;
+  gt_eval<H>(L, N, blockIdx.x, feats, targets, order, P, loss);
+}
+
+// workgroup (i, b): sample i of job model0 + b under that model's slot; a job
+// shorter than the grid's width leaves its spare workgroups idle
+template <int H>
+__global__ __launch_bounds__(kGtT) void gobi_train_eval_many_kernel(const pgp_gobi_job* __restrict__ jobs, int model0,
+                                                                    const float* __restrict__ feats,
+                                                                    const float* __restrict__ targets,
+                                                                    const int* __restrict__ order,
+                                                                    const float* __restrict__ P,
+                                                                    float* __restrict__ loss) {
+  using G = GtGeo<H>;
+  __shared__ GtLds<H> L;
+  const int mdl = model0 + blockIdx.y;
+  const pgp_gobi_job j = jobs[mdl];
+  if ((int)blockIdx.x >= j.n) return;
+  gt_eval<H>(L, j.n_samples, blockIdx.x, feats + j.sample_off * G::IN, targets + j.sample_off * 2,
+             order + j.order_off, P + (size_t)mdl * G::SIZE, loss + j.order_off);
 }
 
 }  // namespace
@@ -376,6 +439,28 @@ hipError_t launch_gobi_train_eval(int n_hosts, int n_samples, int n, const float
   if (n_hosts != 16) return hipErrorInvalidValue;
   gobi_train_eval_kernel<16><<<n, kGtT, 0, st>>>(n_samples, feats, targets, order, P, loss);
   return hipGetLastError();
+}
+
+hipError_t launch_gobi_train_steps_many(int n_hosts, int n_models, const pgp_gobi_job* jobs_dev, const float* feats,
+                                        const float* targets, const int* order, float* P, float* m, float* v,
+                                        float* loss, hipStream_t st) {
+  if (n_hosts != 16) return hipErrorInvalidValue;
+  gobi_train_steps_many_kernel<16><<<n_models, kGtT, 0, st>>>(jobs_dev, feats, targets, order, P, m, v, loss);
+  return hipGetLastError();
+}
+
+hipError_t launch_gobi_train_eval_many(int n_hosts, int n_models, int max_n, const pgp_gobi_job* jobs_dev,
+                                       const float* feats, const float* targets, const int* order, const float* P,
+                                       float* loss, hipStream_t st) {
+  if (n_hosts != 16) return hipErrorInvalidValue;
+  constexpr int kMaxY = 65535;  // the grid's y limit: more models take more launches
+  for (int m0 = 0; m0 < n_models; m0 += kMaxY) {
+    const int my = n_models - m0 < kMaxY ? n_models - m0 : kMaxY;
+    gobi_train_eval_many_kernel<16><<<dim3(max_n, my), kGtT, 0, st>>>(jobs_dev, m0, feats, targets, order, P, loss);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace pgp

@@ -31,10 +31,30 @@ def load_weights(path=_DATA):
     return {k: np.asarray(z[k], dtype=np.float32) for k in _ORDER}, float(z["max_ips"])
 
 
-class GOBIOptimizer:
-    """Batched opt(): init [E,16,18] -> (result [E,16,18], iterations [E], fitness [E])."""
+def _blob(weights) -> np.ndarray:
+    return np.ascontiguousarray(np.concatenate([np.asarray(weights[k], np.float32).reshape(-1) for k in _ORDER]))
 
-    def __init__(self, weights: dict | None = None, device="cuda"):
+
+def check_model_of(model_of, n_env, n_models) -> np.ndarray:
+    """model_of as the int32 [E] array the planner takes; ValueError for another
+    length or an index outside [0, n_models)."""
+    mo = np.asarray(model_of)
+    if mo.ndim != 1 or mo.shape[0] != n_env or (mo.size and not np.issubdtype(mo.dtype, np.integer)):
+        raise ValueError(f"model_of must be {n_env} integers (one per environment), got {mo.dtype} {mo.shape}")
+    if mo.size and (mo.min() < 0 or mo.max() >= n_models):
+        raise ValueError(f"model_of has an index outside [0, {n_models})")
+    return np.ascontiguousarray(mo, dtype=np.int32)
+
+
+class GOBIOptimizer:
+    """Batched opt(): init [E,16,18] -> (result [E,16,18], iterations [E], fitness [E]).
+
+    weights: one state dict, or a list of them (a fleet whose cells have their
+    own surrogates, as the reference's GOBIScheduler.__init__ loads its
+    data_type's own, GOBI.py:11-17); ``optimize(init, model_of=...)`` then runs
+    each environment against its own."""
+
+    def __init__(self, weights: dict | list | None = None, device="cuda"):
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -48,24 +68,79 @@ class GOBIOptimizer:
         L.pgp_gobi_weight_len.argtypes = [ctypes.c_int]
         L.pgp_gobi_weight_len.restype = ctypes.c_size_t
         L.pgp_gobi_create.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
+        # the fleet entries; a PGP_LIB build from before them (an A/B against an older library) serves one model
+        fleet = hasattr(L, "pgp_gobi_create_many")
+        if fleet:
+            L.pgp_gobi_create_many.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
+            L.pgp_gobi_model_count.argtypes = [vp]
+            L.pgp_gobi_set_model.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
+            L.pgp_gobi_optimize_groups.argtypes = [vp, ctypes.c_int, ctypes.c_int] + [vp] * 5 + [ctypes.c_int, vp, vp]
+            L.pgp_gobi_plan_groups.argtypes = [ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int]
         L.pgp_gobi_optimize.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp]
         L.pgp_gobi_destroy.argtypes = [vp]
         L.pgp_gobi_last_error.argtypes = []
         L.pgp_gobi_last_error.restype = ctypes.c_char_p
         self._L = L
-        blob = np.ascontiguousarray(np.concatenate([np.asarray(weights[k], np.float32).reshape(-1) for k in _ORDER]))
-        if blob.size != L.pgp_gobi_weight_len(H):
-            raise ValueError(f"GOBI weight blob {blob.size} != {L.pgp_gobi_weight_len(H)}")
+        many = isinstance(weights, (list, tuple))
+        if many and not weights:
+            raise ValueError("an empty list of surrogates")
+        if many and not fleet:
+            raise _native.NativeError(f"{_native.LIB_PATH} has no pgp_gobi_create_many: a list of surrogates needs it")
+        blobs = [_blob(w) for w in (weights if many else [weights])]
+        for blob in blobs:
+            if blob.size != L.pgp_gobi_weight_len(H):
+                raise ValueError(f"GOBI weight blob {blob.size} != {L.pgp_gobi_weight_len(H)}")
         torch.cuda.set_device(self.device)
         h = vp()
-        rc = L.pgp_gobi_create(H, blob.ctypes.data_as(vp), blob.size, ctypes.byref(h))
+        if many:
+            blob = np.ascontiguousarray(np.stack(blobs))
+            rc = L.pgp_gobi_create_many(H, len(blobs), blob.ctypes.data_as(vp), blob.size, ctypes.byref(h))
+        else:
+            blob = blobs[0]
+            rc = L.pgp_gobi_create(H, blob.ctypes.data_as(vp), blob.size, ctypes.byref(h))
         if rc != 0:
             raise RuntimeError(f"pgp_gobi_create: {rc} {L.pgp_gobi_last_error().decode()}")
         self._h = h
+        self.n_models = int(L.pgp_gobi_model_count(h)) if fleet else 1
+        self._plans = {}   # model_of's bytes -> (device table, groups)
 
-    def optimize(self, init, out=None, stream=None, max_iters=0, pre=None):
+    def set_model(self, m, weights):
+        """Replace surrogate m (a cell whose surrogate was retrained).  A
+        blocking upload: call it between optimisations, not during one."""
+        if not 0 <= int(m) < self.n_models:
+            raise IndexError(f"model {m} outside [0, {self.n_models})")
+        blob = _blob(weights)
+        if blob.size != self._L.pgp_gobi_weight_len(H):
+            raise ValueError(f"GOBI weight blob {blob.size} != {self._L.pgp_gobi_weight_len(H)}")
+        torch.cuda.set_device(self.device)
+        rc = self._L.pgp_gobi_set_model(self._h, int(m), blob.ctypes.data_as(ctypes.c_void_p), blob.size)
+        if rc != 0:
+            raise RuntimeError(f"pgp_gobi_set_model: {rc} {self._L.pgp_gobi_last_error().decode()}")
+
+    def plan(self, model_of, n_env):
+        """The device group table of a model_of [E] (pgp_gobi_plan_groups),
+        cached by its content: (int32 tensor [G,5], G)."""
+        mo = check_model_of(model_of, n_env, self.n_models)
+        key = mo.tobytes()
+        hit = self._plans.get(key)
+        if hit is None:
+            cap = (n_env + 3) // 4 + self.n_models
+            table = np.empty((cap, 5), dtype=np.int32)
+            vp = ctypes.c_void_p
+            g = self._L.pgp_gobi_plan_groups(n_env, mo.ctypes.data_as(vp), self.n_models, table.ctypes.data_as(vp), cap)
+            if g < 0:
+                raise RuntimeError(f"pgp_gobi_plan_groups: {g} {self._L.pgp_gobi_last_error().decode()}")
+            if len(self._plans) >= 16:   # a fleet has a few assignments; do not grow without bound
+                self._plans.clear()
+            hit = self._plans[key] = (torch.as_tensor(table[:g].copy()).to(self.device), g)
+        return hit
+
+    def optimize(self, init, out=None, stream=None, max_iters=0, pre=None, model_of=None, groups=None):
         """init: [E,16,18] float32 (device tensor or host array).  max_iters /
-        pre [E,16,16]: test hooks (step limit, pre-projection values)."""
+        pre [E,16,16]: test hooks (step limit, pre-projection values).
+        model_of: int [E], environment e's surrogate (None: all on model 0);
+        its group table is planned once per content.  groups: a ready device
+        table [G,5] int32 instead (see pgp_gobi_optimize_groups)."""
         x = torch.as_tensor(init, dtype=torch.float32).to(self.device).contiguous()
         if x.dim() != 3 or tuple(x.shape[1:]) != (H, H + 2):
             raise ValueError(f"init must be [E,{H},{H + 2}], got {tuple(x.shape)}")
@@ -75,6 +150,22 @@ class GOBIOptimizer:
                    torch.empty(E, dtype=torch.float32, device=self.device))
         res, its, fit = out
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if model_of is not None and groups is not None:
+            raise ValueError("model_of or groups, not both")
+        if model_of is not None or groups is not None:
+            if groups is None:
+                groups, g = self.plan(model_of, E)
+            else:
+                if groups.dtype != torch.int32 or groups.dim() != 2 or groups.shape[1] != 5 or not groups.is_cuda:
+                    raise ValueError("groups must be a device int32 tensor [G,5]")
+                groups, g = groups.contiguous(), int(groups.shape[0])
+            rc = self._L.pgp_gobi_optimize_groups(self._h, E, g, groups.data_ptr(), x.data_ptr(), res.data_ptr(),
+                                                  its.data_ptr(), fit.data_ptr(), int(max_iters),
+                                                  None if pre is None else pre.data_ptr(),
+                                                  ctypes.c_void_p(st.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"pgp_gobi_optimize_groups: {rc} {self._L.pgp_gobi_last_error().decode()}")
+            return res, its, fit
         rc = self._L.pgp_gobi_optimize(self._h, E, x.data_ptr(), res.data_ptr(), its.data_ptr(), fit.data_ptr(),
                                        int(max_iters), None if pre is None else pre.data_ptr(),
                                        ctypes.c_void_p(st.cuda_stream))

@@ -13,6 +13,10 @@ the gradient, not the decoupled AdamW of ``pgp_adamw``).  Here a whole
 (csrc/pgp_gobitrain.hip) over the dataset uploaded once, and ``accuracy``
 (train.py:33-42) one launch of ``pgp_gobi_train_eval``.  All of it is fp32, as
 the reference's model and features are.
+
+``GOBIFleetTrainer`` trains M surrogates at once, one workgroup each in one
+``pgp_gobi_train_steps_many`` launch (a fleet's cells, or a seed / learning-rate
+sweep over one dataset), every model with the bits of a lone ``GOBITrainer``.
 """
 from __future__ import annotations
 
@@ -279,3 +283,267 @@ class GOBITrainer:
         """torch.save of checkpoint() (train.py:44-50; the reference names the
         file checkpoints/energy_latency_16_<epoch>.ckpt)."""
         torch.save(self.checkpoint(epoch, accuracy_list), path)
+
+
+# ---- a fleet of surrogates: M models trained in one launch (DESIGN §21) ----
+
+# pgp_gobi_job of include/preganplus.h (72 bytes, no padding)
+JOB_DTYPE = np.dtype([("sample_off", "<i8"), ("order_off", "<i8"), ("step0", "<i8"), ("n_samples", "<i4"),
+                      ("n", "<i4"), ("lr", "<f8"), ("weight_decay", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"),
+                      ("eps", "<f8")])
+_HYPER_KEYS = ("lr", "weight_decay", "beta1", "beta2", "eps")
+
+
+def _blob_of(weights):
+    for k in _ORDER:
+        if tuple(np.shape(weights[k])) != SHAPES[k]:
+            raise ValueError(f"{k}: shape {tuple(np.shape(weights[k]))}, expected {SHAPES[k]}")
+    return np.concatenate([np.asarray(weights[k], dtype=np.float32).reshape(-1) for k in _ORDER])
+
+
+def fleet_state(weights=None, seeds=None, states=None, hyper=None):
+    """The host side of GOBIFleetTrainer's construction (no device needed):
+    (P, m, v [M, 61890] float32, steps [M], hypers: M dicts of lr /
+    weight_decay / beta1 / beta2 / eps).  Exactly one of weights (a list of
+    ``_ORDER`` dicts) and seeds (``fresh_weights(seed)`` each); states: None or
+    one ``optimizer_state_dict`` (or None) per model; hyper: None, one dict for
+    all, or one per model (over a checkpoint's own values)."""
+    if (weights is None) == (seeds is None):
+        raise ValueError("pass weights=[...] or seeds=[...], one of them")
+    ws = [fresh_weights(s) for s in seeds] if weights is None else list(weights)
+    M = len(ws)
+    if M == 0:
+        raise ValueError("an empty fleet")
+    if states is None:
+        states = [None] * M
+    if len(states) != M:
+        raise ValueError(f"{len(states)} optimizer states for {M} models")
+    if hyper is None or isinstance(hyper, dict):
+        hyper = [hyper] * M
+    if len(hyper) != M:
+        raise ValueError(f"{len(hyper)} hyper-parameter sets for {M} models")
+    P = np.stack([_blob_of(w) for w in ws])
+    m, v = np.zeros_like(P), np.zeros_like(P)
+    steps, hypers = [0] * M, []
+    for i in range(M):
+        hy = {"lr": LR, "weight_decay": WEIGHT_DECAY, "beta1": BETAS[0], "beta2": BETAS[1], "eps": EPS}
+        st = states[i]
+        if st and st.get("state"):
+            seen, off = set(), 0
+            for idx, k in enumerate(_ORDER):
+                cnt = int(np.prod(SHAPES[k]))
+                s = st["state"][idx]
+                m[i, off:off + cnt] = np.asarray(s["exp_avg"], dtype=np.float32).reshape(-1)
+                v[i, off:off + cnt] = np.asarray(s["exp_avg_sq"], dtype=np.float32).reshape(-1)
+                seen.add(int(s["step"]))
+                off += cnt
+            if len(seen) != 1:
+                raise ValueError(f"model {i}: optimizer state with different step counts per tensor: {sorted(seen)}")
+            steps[i] = seen.pop()
+            g = st["param_groups"][0]
+            hy.update(lr=g["lr"], weight_decay=g["weight_decay"], eps=g["eps"], beta1=g["betas"][0],
+                      beta2=g["betas"][1])
+        if hyper[i]:
+            unknown = set(hyper[i]) - set(_HYPER_KEYS)
+            if unknown:
+                raise ValueError(f"unknown hyper-parameters {sorted(unknown)}; known: {_HYPER_KEYS}")
+            hy.update(hyper[i])
+        hypers.append(hy)
+    return P, m, v, steps, hypers
+
+
+def pool_datasets(datasets, dataset_of, n_models):
+    """One sample pool from a list of (feats [N,16,18], targets [N,2]):
+    (feats fp32 [Ntot,16,18], targets fp32 [Ntot,2], offsets, sizes,
+    dataset_of [n_models]).  dataset_of None: model m trains on dataset m, or
+    every model on the only one."""
+    datasets = list(datasets)
+    if not datasets:
+        raise ValueError("no dataset")
+    fs, ts = [], []
+    for i, (f, t) in enumerate(datasets):
+        f, t = np.asarray(f, dtype=np.float32), np.asarray(t, dtype=np.float32)
+        if f.ndim != 3 or f.shape[1:] != (H, H + 2) or t.shape != (f.shape[0], 2):
+            raise ValueError(f"dataset {i}: feats must be [N,{H},{H + 2}] and targets [N,2], got {f.shape}, {t.shape}")
+        fs.append(f)
+        ts.append(t)
+    if dataset_of is None:
+        if len(datasets) == 1:
+            dataset_of = [0] * n_models
+        elif len(datasets) == n_models:
+            dataset_of = list(range(n_models))
+        else:
+            raise ValueError(f"{len(datasets)} datasets for {n_models} models: say which with dataset_of")
+    dataset_of = [int(d) for d in dataset_of]
+    if len(dataset_of) != n_models:
+        raise ValueError(f"dataset_of has {len(dataset_of)} entries for {n_models} models")
+    if any(d < 0 or d >= len(datasets) for d in dataset_of):
+        raise ValueError(f"dataset_of has an index outside [0, {len(datasets)})")
+    sizes = [int(f.shape[0]) for f in fs]
+    offsets = [int(x) for x in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
+    return np.concatenate(fs), np.concatenate(ts), offsets, sizes, dataset_of
+
+
+def fleet_jobs(orders, sample_off, n_samples, steps, hypers):
+    """The job table (JOB_DTYPE [M]) and the order pool (int32) of one call:
+    model m's order list, relative to its own dataset, goes to the pool at
+    order_off = the lengths before it.  IndexError for an index outside the
+    model's dataset (as GOBITrainer), ValueError for another number of lists."""
+    M = len(steps)
+    if len(orders) != M:
+        raise ValueError(f"{len(orders)} order lists for {M} models")
+    jobs = np.zeros(M, dtype=JOB_DTYPE)
+    pool, off = [], 0
+    for i in range(M):
+        o = np.asarray(orders[i], dtype=np.int64).reshape(-1)
+        if o.size and (o.min() < 0 or o.max() >= n_samples[i]):
+            raise IndexError(f"model {i}: sample index outside [0, {n_samples[i]})")
+        jobs[i] = (sample_off[i], off, steps[i], n_samples[i], o.size) + tuple(hypers[i][k] for k in _HYPER_KEYS)
+        pool.append(o.astype(np.int32))
+        off += o.size
+    return jobs, (np.concatenate(pool) if pool else np.zeros(0, np.int32))
+
+
+class GOBIFleetTrainer:
+    """M surrogates on the device, one slot each of P / m / v [M, 61890], trained
+    by ``pgp_gobi_train_steps_many``: one workgroup per model, every model's
+    bits those of a lone ``GOBITrainer`` with its settings.  The reference keeps
+    a surrogate per environment (one dataset and checkpoint per data_type,
+    scheduler/BaGTI/); the same entry serves a seed / learning-rate sweep over
+    one dataset.  See ``fleet_state`` for the arguments."""
+
+    def __init__(self, weights=None, seeds=None, states=None, hyper=None, device="cuda"):
+        P, m, v, self.steps, self.hypers = fleet_state(weights, seeds, states, hyper)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("GOBIFleetTrainer runs on the GPU only (no CPU fallback)")
+        self._L = bind_many(_native.lib())
+        self.n_models = int(P.shape[0])
+        assert P.shape[1] == self._L.pgp_gobi_weight_len(H)
+        with torch.cuda.device(self.device):
+            self.P = torch.tensor(P, device=self.device)
+            self.m = torch.tensor(m, device=self.device)
+            self.v = torch.tensor(v, device=self.device)
+            self._jobs_dev = torch.empty(self.n_models * JOB_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.feats = self.targets = None
+
+    def set_data(self, datasets, dataset_of=None):
+        """Upload the datasets once as one pool; models may share entries."""
+        f, t, self._off, self._size, self.dataset_of = pool_datasets(datasets, dataset_of, self.n_models)
+        self.feats = torch.as_tensor(f).to(self.device).contiguous()
+        self.targets = torch.as_tensor(t).to(self.device).contiguous()
+
+    def n_samples(self, m):
+        return self._size[self.dataset_of[m]]
+
+    def _launch(self, orders, train):
+        if self.feats is None:
+            raise RuntimeError("no dataset: call set_data(datasets) first")
+        M = self.n_models
+        jobs, pool = fleet_jobs(orders, [self._off[self.dataset_of[i]] for i in range(M)],
+                                [self.n_samples(i) for i in range(M)], self.steps, self.hypers)
+        order = torch.as_tensor(pool).to(self.device)
+        loss = torch.empty(int(pool.size), dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        st = vp(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            if train:
+                _native.check(self._L.pgp_gobi_train_steps_many(
+                    H, M, jobs.ctypes.data_as(vp), int(self.feats.shape[0]), self.feats.data_ptr(),
+                    self.targets.data_ptr(), int(pool.size), order.data_ptr(), self.P.data_ptr(), self.m.data_ptr(),
+                    self.v.data_ptr(), loss.data_ptr(), self._jobs_dev.data_ptr(), st), "pgp_gobi_train_steps_many")
+            else:
+                _native.check(self._L.pgp_gobi_train_eval_many(
+                    H, M, jobs.ctypes.data_as(vp), int(self.feats.shape[0]), self.feats.data_ptr(),
+                    self.targets.data_ptr(), int(pool.size), order.data_ptr(), self.P.data_ptr(), loss.data_ptr(),
+                    self._jobs_dev.data_ptr(), st), "pgp_gobi_train_eval_many")
+        out = loss.cpu().numpy()   # also the point up to which `jobs` (read by the stream's copy) must live
+        return [out[int(j["order_off"]):int(j["order_off"]) + int(j["n"])].copy() for j in jobs], jobs
+
+    def backprop(self, orders):
+        """train.py:18-31 for every model over its own order list (relative to
+        its own dataset; an empty list leaves the model untouched), all in one
+        launch.  Returns the per-sample fp32 losses, one array per model."""
+        losses, jobs = self._launch(orders, True)
+        for i in range(self.n_models):
+            self.steps[i] += int(jobs[i]["n"])
+        return losses
+
+    def accuracy(self, orders):
+        """train.py:33-42 for every model: the per-sample losses of its list."""
+        return self._launch(orders, False)[0]
+
+    def train(self, epochs, rngs):
+        """The epoch loop of train.py:78-91 per model (set_data first): model m
+        has its own ``random.Random`` rngs[m], its own persistent shuffled list
+        and its own 80/20 split; each epoch is one training launch and one
+        evaluation launch for the whole fleet.  Returns the accuracy lists,
+        [[(test, train), ...] per model]; the orders taken are in
+        ``self.orders[m]``."""
+        M = self.n_models
+        if len(rngs) != M:
+            raise ValueError(f"{len(rngs)} random generators for {M} models")
+        if self.feats is None:
+            raise RuntimeError("no dataset: call set_data(datasets) first")
+        idx = [list(range(self.n_samples(i))) for i in range(M)]
+        split = [int(0.8 * self.n_samples(i)) for i in range(M)]
+        acc = [[] for _ in range(M)]
+        self.orders = [[] for _ in range(M)]
+        for _ in range(epochs):
+            for i in range(M):
+                rngs[i].shuffle(idx[i])
+                self.orders[i].append(list(idx[i]))
+            tr = self.backprop([idx[i][:split[i]] for i in range(M)])
+            te = self.accuracy([idx[i][split[i]:] for i in range(M)])
+            for i in range(M):
+                acc[i].append((GOBITrainer._mean(te[i]), GOBITrainer._mean(tr[i])))
+        return acc
+
+    def _tensors(self):
+        out, off = [], 0
+        for k in _ORDER:
+            cnt = int(np.prod(SHAPES[k]))
+            out.append((k, off, cnt))
+            off += cnt
+        return out
+
+    def weights_numpy(self, m) -> dict:
+        p = self.P[m].detach().cpu().numpy()
+        return {k: p[o:o + cnt].reshape(SHAPES[k]).copy() for k, o, cnt in self._tensors()}
+
+    def checkpoint(self, m, epoch, accuracy_list):
+        """save_model's dict (train.py:44-50) of model m."""
+        hy = self.hypers[m]
+        return checkpoint_dict(self.P[m].cpu().numpy(), self.m[m].cpu().numpy(), self.v[m].cpu().numpy(),
+                               self.steps[m], epoch, accuracy_list, hy["lr"], hy["weight_decay"],
+                               (hy["beta1"], hy["beta2"]), hy["eps"])
+
+    def save(self, m, path, epoch=0, accuracy_list=()):
+        torch.save(self.checkpoint(m, epoch, accuracy_list), path)
+
+    def trainer(self, m) -> GOBITrainer:
+        """An ordinary GOBITrainer holding copies of model m's parameters,
+        moments, step count, hyper-parameters and (if set) dataset: it goes on
+        as a checkpoint of model m would."""
+        t = GOBITrainer(weights=self.weights_numpy(m), device=self.device)
+        t.m, t.v, t.step = self.m[m].clone(), self.v[m].clone(), self.steps[m]
+        hy = self.hypers[m]
+        t.lr, t.wd, t.b1, t.b2, t.eps = hy["lr"], hy["weight_decay"], hy["beta1"], hy["beta2"], hy["eps"]
+        if self.feats is not None:
+            o, n = self._off[self.dataset_of[m]], self.n_samples(m)
+            t.feats, t.targets, t.n_samples = self.feats[o:o + n].clone(), self.targets[o:o + n].clone(), n
+        return t
+
+
+def bind_many(L):
+    """argtypes of the fleet entries (once per library)."""
+    if not getattr(L, "_pgp_gobifleet_bound", False):
+        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+        L.pgp_gobi_weight_len.argtypes = [i32]
+        L.pgp_gobi_weight_len.restype = ctypes.c_size_t
+        L.pgp_gobi_train_steps_many.argtypes = [i32, i32, vp, i64, vp, vp, i64] + [vp] * 7
+        L.pgp_gobi_train_steps_many.restype = i32
+        L.pgp_gobi_train_eval_many.argtypes = [i32, i32, vp, i64, vp, vp, i64] + [vp] * 5
+        L.pgp_gobi_train_eval_many.restype = i32
+        L._pgp_gobifleet_bound = True
+    return L
