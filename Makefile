@@ -8,7 +8,7 @@ KSRCS := $(CSRC)/pgp_tunef.hip $(CSRC)/pgp_dec.hip $(CSRC)/pgp_gat.hip $(CSRC)/p
 SRCS := $(KSRCS) $(CSRC)/pgp_pack.cpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
-HDRS := include/preganplus.h $(CSRC)/pgp_tunef.hpp $(CSRC)/pgp_layout.hpp $(CSRC)/pgp_pack.hpp $(CSRC)/pgp_device.hpp $(CSRC)/pgp_train.hpp $(CSRC)/pgp_tune.hpp $(CSRC)/pgp_tunedp.hpp $(CSRC)/pgp_tunetargets.hpp $(CSRC)/pgp_gemm.hpp $(CSRC)/pgp_packcore.hpp $(CSRC)/pgp_repack.hpp $(CSRC)/pgp_philox.hpp
+HDRS := include/preganplus.h $(CSRC)/pgp_tunef.hpp $(CSRC)/pgp_layout.hpp $(CSRC)/pgp_pack.hpp $(CSRC)/pgp_device.hpp $(CSRC)/pgp_train.hpp $(CSRC)/pgp_tune.hpp $(CSRC)/pgp_tunedp.hpp $(CSRC)/pgp_tunetargets.hpp $(CSRC)/pgp_gemm.hpp $(CSRC)/pgp_packcore.hpp $(CSRC)/pgp_repack.hpp $(CSRC)/pgp_philox.hpp $(CSRC)/pgp_encoder_body.inc
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 
 .PHONY: all clean resource-usage variant asan

@@ -169,11 +169,18 @@ int pgp_embedding(int n_hosts, int batch, const float* logits, const float* prot
  * tools/micro/bf16_split.hip); on = 0: v_mfma_f32_16x16x4_f32.  Returns
  * PGP_ERR_UNSUPPORTED for on = 1 where the split form is not compiled. */
 int pgp_decoder_split(pgp_model* m, int on);
-/* K2's feed-forward form, likewise (the default where compiled: H = 50, the
- * tail-resident encoder): both layers' linear1 / linear2 as split-bf16 MFMAs
- * (planes derived on the device at each weight load / repack); on = 0: the
- * fp32 MFMA. */
+/* K2's form, likewise (H = 50, the tail-resident encoder; planes derived on the
+ * device at each weight load / repack).  on = 0: the fp32 MFMA throughout;
+ * on = 1 (the default): the best split form compiled: both layers' linear1 /
+ * linear2 and layer 1's q|k, v and out_proj as split-bf16 MFMAs, the planes
+ * that do not fit the LDS read from global memory once per unit; on = 2: the
+ * feed-forward alone on split-bf16 MFMAs.  PGP_ERR_ARG for any other value. */
 int pgp_encoder_split(pgp_model* m, int on);
+/* Geometry of form 1's attention-split kernel as built for n_hosts: whether it
+ * is compiled (otherwise form 1 runs form 2's kernel and the rest is 0), its
+ * static LDS bytes, and how many of layer 1's attention plane triples stay in
+ * LDS / are read from the global image. */
+int pgp_encoder_form_info(int n_hosts, int* compiled, int* lds_bytes, int* resident_triples, int* streamed_triples);
 /* K3's contraction form, likewise (the default where compiled: H = 16, 50; also
  * the FPE variant's K3): Gen1, Disc1 and Gen2 as split-bf16 MFMAs, a schedule
  * block exactly representable in bf16 (one-hot GOBI rows) in three products

@@ -90,6 +90,9 @@ def lib():
     L.pgp_decoder_split.restype = c_int
     L.pgp_encoder_split.argtypes = [vp, c_int]
     L.pgp_encoder_split.restype = c_int
+    if hasattr(L, "pgp_encoder_form_info"):  # absent from an earlier build selected with PGP_LIB (tools/ab_bench.py)
+        L.pgp_encoder_form_info.argtypes = [c_int] + [ctypes.POINTER(c_int)] * 4
+        L.pgp_encoder_form_info.restype = c_int
     L.pgp_gan_split.argtypes = [vp, c_int]
     L.pgp_gan_split.restype = c_int
     L.pgp_schedule_onehot.argtypes = [c_int, c_int, fp, fp, vp]

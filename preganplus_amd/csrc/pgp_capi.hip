@@ -16,6 +16,11 @@
 #include "pgp_tunef.hpp"
 #include "pgp_tunedp.hpp"
 
+// K2's default form (pgp_encoder_split); an A/B build sets 2
+#ifndef PGP_ENC_FORM
+#define PGP_ENC_FORM 1
+#endif
+
 #include <vector>
 
 using namespace pgp;
@@ -27,7 +32,7 @@ struct pgp_model {
   float* d_frags = nullptr;
   float* d_decb = nullptr;   // split-bf16 decoder planes (derived from d_frags on the device)
   float* d_encb = nullptr;   // split-bf16 encoder LDS image (derived likewise)
-  bool enc_split = true;     // K2's feed-forward on the split-bf16 planes where compiled (pgp_encoder_split)
+  int enc_form = PGP_ENC_FORM;  // K2 (pgp_encoder_split): 0 fp32, 1 the best split form compiled, 2 the split feed-forward alone
   bool dec_split = true;     // K2b on the split-bf16 planes where compiled (pgp_decoder_split)
   float* d_ganb = nullptr;   // split-bf16 GAN planes (derived from d_frags on the device)
   bool gan_split = true;     // K3 on the split-bf16 planes where compiled (pgp_gan_split)
@@ -221,7 +226,8 @@ int pgp_forward_stage(pgp_model* m, int stage, int batch, const float* windows, 
   a.emb = m->d_emb;
   a.frags = m->d_frags;
   a.decb = m->dec_split ? m->d_decb : nullptr;
-  a.encb = m->enc_split ? m->d_encb : nullptr;
+  a.encb = m->enc_form ? m->d_encb : nullptr;
+  a.enc_form = m->enc_form;
   a.ganb = m->gan_split ? m->d_ganb : nullptr;
   a.tab = m->d_tab;
   a.gtab = m->d_gtab;
@@ -334,7 +340,15 @@ int pgp_encoder_split(pgp_model* m, int on) {
   if (!m) return fail(PGP_ERR_ARG, "NULL model");
   if (m->fpe || encoder_split_floats(m->H) == 0)
     return on ? fail(PGP_ERR_UNSUPPORTED, "split-bf16 encoder not compiled for this model / host count") : PGP_OK;
-  m->enc_split = on != 0;
+  if (on < 0 || on > 2) return fail(PGP_ERR_ARG, "encoder form: 0 (fp32), 1 (best split form) or 2 (split feed-forward)");
+  m->enc_form = on;
+  return PGP_OK;
+}
+
+int pgp_encoder_form_info(int n_hosts, int* compiled, int* lds_bytes, int* resident_triples, int* streamed_triples) {
+  if (!compiled || !lds_bytes || !resident_triples || !streamed_triples) return fail(PGP_ERR_ARG, "NULL output");
+  *compiled = encoder_asplit(n_hosts) ? 1 : 0;
+  encoder_asplit_geometry(n_hosts, lds_bytes, resident_triples, streamed_triples);
   return PGP_OK;
 }
 

@@ -34,6 +34,10 @@ inline int device_cus() {
 // Kernel arguments shared by the launches of one forward call.
 struct FwdArgs {
   int B, H, K;
+  // K2 with encb set: 1 = the attention-split form (encoder_asplit_kernel; its image follows EncS in encb),
+  // otherwise the split feed-forward alone.  In the padding before the pointers: no field of the launches' kernel
+  // arguments moves.
+  int enc_form;
   const float* windows;  // [B,3,3H]
   const float* sched;    // [B,H,H]
   float* agg;            // workspace: GAT output, [blk][H][3][48]
@@ -114,8 +118,14 @@ hipError_t launch_decoder(const FwdArgs& a, hipStream_t st);
 // fp32 decoder runs at this H) and their derivation from the fp32 fragments
 long decoder_split_floats(int H);
 hipError_t launch_decoder_split(int H, const float* frags, float* decb, hipStream_t st);
-long encoder_split_floats(int H);  // 0: no split-bf16 encoder at this H
+// floats of the split-bf16 encoder images (EncS, then EncA where the attention-split form is compiled); 0: no
+// split-bf16 encoder at this H.  launch_encoder_split derives every image.
+long encoder_split_floats(int H);
 hipError_t launch_encoder_split(int H, const float* frags, float* encb, hipStream_t st);
+// the attention-split form (encoder_asplit_kernel): compiled at this H; its geometry as built (static LDS bytes
+// of the kernel, plane triples of layer 1's attention kept in LDS / read from the global image per unit)
+bool encoder_asplit(int H);
+void encoder_asplit_geometry(int H, int* lds_bytes, int* resident, int* streamed);
 hipError_t launch_gan(const FwdArgs& a, hipStream_t st);
 // K3 on split-bf16 MFMAs (pgp_gansplit.hip): plane floats (0: not compiled at
 // this H), their derivation from the fp32 fragments, the launch

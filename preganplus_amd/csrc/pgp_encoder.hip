@@ -9,7 +9,11 @@
 //   layer 1) are loaded once into one 8-wave workgroup per CU; each wave takes
 //   an equal contiguous range of the (16-window block, host) units (hosts are
 //   independent here) and prefetches the next unit's raw features through a
-//   per-wave LDS slot; no barrier in the host loop;
+//   per-wave LDS slot; no barrier in the host loop.  Three forms: fp32 MFMAs
+//   throughout, the feed-forward on split-bf16 MFMAs (EncS), and (the default,
+//   a kernel of its own: encoder_asplit_kernel) layer 1's attention
+//   projections split too, the planes that do not fit the LDS read per unit
+//   from global memory (EncA);
 // * resident (H <= 16): both layers' weights in LDS, one 16-window block per
 //   wave, host loop without barriers;
 // * ring (other H): stages stream through a 2-slot LDS ring by
@@ -87,18 +91,45 @@ struct EncS {
   static constexpr long SIZE = STREAM;           // the device image (floats)
 };
 
+// Attention-split form (encoder_asplit_kernel): layer 1's q|k, v and out_proj
+// GEMMs on the split planes too, 32-k blocks pairing fp32 groups 2b, 2b + 1 as
+// above.  Its image: layer 0's FFN planes | layer 1's FFN planes | layer 1's
+// attention as NT plane triples in consumption order: q|k [b][m] (the 2*TQ q
+// and k tiles), v [b][t], out_proj [b][mt].  The 72 attention groups do not fit
+// the LDS beside the FFN planes and the tables (156 KiB + 20 KiB), so the
+// workgroup keeps triples [0, NRES) there and every wave reads the last
+// NT - NRES (v's last one and out_proj) once per unit from the global image
+// with 16-byte loads: 21 KiB that every CU re-reads, L2 hits.
+template <int H>
+struct EncA {
+  using G = Geo<H>;
+  using S = EncS<H>;
+  static constexpr int NBD = S::NBD;                // 32-k blocks over d
+  static constexpr int NBO = cdiv(G::KQ_OT, 2);     // 32-k blocks over the O slots
+  static constexpr int TQK = 2 * G::TQ * NBD, TV = G::TQ * NBD, TO = G::MT_X * NBO;
+  static constexpr int NT = TQK + TV + TO;
+  static constexpr int NRES = TQK + TV - 1;         // LDS-resident triples
+  static constexpr int L0F = 0, L1F = S::FFN, L1A = 2 * S::FFN;
+  static constexpr int RES_G = L1A + 3 * NRES;      // groups in LDS
+  static constexpr int GROUPS = L1A + 3 * NT;
+  static constexpr long SIZE = (long)GROUPS * G::FQ;  // the device image (floats)
+};
+
 // RESIDENT (H <= 16): both layers' weights (24 KB at H = 16) are loaded into LDS
 // once per workgroup; the host loop then runs with no ring barriers or DMAs.
 // Tail-resident: groups [RES0, 2*LAYER_G) of the stream (see tail_res), or the
-// split image (EncS).
-template <int H, bool SPLIT = false>
+// split image (EncS), or the resident part of the attention-split one (EncA).
+template <int H, bool SPLIT = false, bool AS = false>
 struct EncLds {
+  static_assert(SPLIT || !AS, "the attention-split form includes the split feed-forward");
   static constexpr bool TRES = tail_res<H>();
   // the tail-resident mode has no barrier in the host loop: waves take
   // (block, host) unit ranges and prefetch through an LDS slot (at H <= 16,
   // also resident, that measured slower: fleet 1.97 -> 2.00 ms)
   static constexpr int RES0 = TRES ? Geo<H>::st_begin(Geo<H>::NST - 1) : 0;  // layer 0 stage 2
-  static constexpr int STREAM = SPLIT ? EncS<H>::STREAM : (kLayers * Geo<H>::LAYER_G - RES0) * Geo<H>::FQ;  // floats
+  static constexpr int STREAM = AS      ? EncA<H>::RES_G * Geo<H>::FQ
+                                : SPLIT ? EncS<H>::STREAM
+                                        : (kLayers * Geo<H>::LAYER_G - RES0) * Geo<H>::FQ;  // floats
   static constexpr bool RESIDENT = TRES || STREAM * 4 <= 32 * 1024;
   static constexpr int SLOT = Geo<H>::SLOT_G * Geo<H>::FQ;
   static constexpr int TAB = Geo<H>::t_size(kMaxProtos);
@@ -109,6 +140,83 @@ struct EncLds {
 template <int H>
 constexpr bool enc_split() {
   return tail_res<H>() && EncLds<H, true>::TOTAL * 4 + enc_waves<H>() * 144 * 4 <= 160 * 1024;
+}
+
+template <int H>
+constexpr int enc_asplit_lds_bytes() {
+  return EncLds<H, true, true>::TOTAL * 4 + enc_waves<H>() * 144 * 4;
+}
+template <int H>
+constexpr bool enc_asplit() {
+  return enc_split<H>() && enc_asplit_lds_bytes<H>() <= 160 * 1024;
+}
+
+// the lane's 8 values of fp32 groups q0, q1 (q1 < 0: zeros) as three planes
+PGP_DEV void split_groups(const float* src, long q0, long q1, float* dst, int lane) {
+  float v[8];
+  const f32x4 x0 = ld4(src + q0 * 256 + lane * 4);
+  const f32x4 x1 = q1 >= 0 ? ld4(src + q1 * 256 + lane * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = x0[e];
+    v[4 + e] = x1[e];
+  }
+  u32x4 p[3];
+  split8(v, p);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(dst + k * 256 + lane * 4) = p[k];
+}
+
+// fp32 stream -> the attention-split image (EncA): one wave per plane triple
+template <int H>
+__global__ __launch_bounds__(256) void enc_asplit_kernel(const float* __restrict__ enc, float* __restrict__ out) {
+  using G = Geo<H>;
+  using S = EncS<H>;
+  using A = EncA<H>;
+  constexpr int T1 = G::MT_F * S::NBD, T2 = G::MT_X * S::NBF, TL = T1 + T2;  // FFN triples per layer
+  const long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (f >= 2 * TL + A::NT) return;
+  const float* src;
+  long q0, q1, dst;
+  if (f < 2 * TL) {  // as enc_split_kernel
+    const int l = (int)(f / TL), t = (int)(f % TL);
+    src = enc + (long)(l * G::LAYER_G + G::P_F1) * 256;
+    const long base = l == 0 ? A::L0F : A::L1F;
+    if (t < T1) {
+      const int c = t / S::NBD, b = t % S::NBD;
+      q0 = c * G::KQ_D + 2 * b;
+      q1 = 2 * b + 1 < G::KQ_D ? q0 + 1 : -1;
+      dst = base + (long)t * 3;
+    } else {
+      const int u = t - T1, m = u / S::NBF, b = u % S::NBF;
+      q0 = G::G_F1 + m * G::KQ_F + 2 * b;
+      q1 = q0 + 1;
+      dst = base + S::F1S + (long)u * 3;
+    }
+  } else {  // layer 1's attention: triple t = block b of tile m of its GEMM
+    const int t = (int)(f - 2 * TL);
+    src = enc + (long)G::LAYER_G * 256;
+    int b, kq;
+    if (t < A::TQK) {
+      b = t / (2 * G::TQ);
+      kq = G::KQ_D;
+      q0 = (t % (2 * G::TQ)) * G::KQ_D + 2 * b;
+    } else if (t < A::TQK + A::TV) {
+      const int u = t - A::TQK;
+      b = u / G::TQ;
+      kq = G::KQ_D;
+      q0 = G::P_V + (u % G::TQ) * G::KQ_D + 2 * b;
+    } else {
+      const int u = t - A::TQK - A::TV;
+      b = u / G::MT_X;
+      kq = G::KQ_OT;
+      q0 = G::P_OT + (u % G::MT_X) * G::KQ_OT + 2 * b;
+    }
+    q1 = 2 * b + 1 < kq ? q0 + 1 : -1;
+    dst = A::L1A + (long)t * 3;
+  }
+  split_groups(src, q0, q1, out + dst * 256, lane);
 }
 
 // fp32 stream -> the split image: one wave per FFN plane triple or fp32 group
@@ -187,6 +295,138 @@ PGP_DEV float relu_enc(float x) {
 // slots ahead of a VALU stream
 PGP_DEV void prio_mfma() { __builtin_amdgcn_s_setprio(1); }
 PGP_DEV void prio_valu() { __builtin_amdgcn_s_setprio(0); }
+
+// plane triple t of layer 1's attention (EncA; t is a constant where this is
+// inlined): from the LDS image AL, or past NRES from the global image AG
+template <int H>
+PGP_DEV void att_planes(const float* AL, const float* __restrict__ AG, int t, int lane, u32x4 (&w)[3]) {
+  // the lane's byte offset re-derived at each use (opaque to the optimiser, as
+  // dma_groups): otherwise a per-lane address per plane is kept across the unit
+  // loop (42 VGPRs for the global ones, spilled)
+  unsigned off = (unsigned)lane * 16u;
+  asm volatile("" : "+v"(off));
+  if (t < EncA<H>::NRES) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      w[k] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(AL + (t * 3 + k) * 256) + off);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      w[k] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(AG + (t * 3 + k) * 256) + off);
+  }
+}
+// the first D triples of a GEMM whose triples are [T0, T0 + NTR), read ahead of
+// whatever the caller puts between this and att_gemm
+template <int H, int T0, int NTR, int D>
+PGP_DEV void att_prologue(const float* AL, const float* AG, int lane, u32x4 (&wq)[NTR][3]) {
+  __builtin_amdgcn_sched_barrier(0);  // not hoisted into the VALU phase before (its registers are the kernel's peak)
+#pragma unroll
+  for (int t = 0; t < D && t < NTR; ++t) att_planes<H>(AL, AG, T0 + t, lane, wq[t]);
+  __builtin_amdgcn_sched_barrier(0);
+}
+// NR VALU rows over B k-steps of groups 2b, 2b + 1 (gemm3_rows' FMAs, in its order)
+template <int KQ, int KS, int NB, int NR>
+PGP_DEV void att_rows(float (&racc)[NR][3], const float* RW, const f32x4 (&Bx)[NB][3], int b, int w, int g) {
+#pragma unroll
+  for (int q4 = 2 * b; q4 < 2 * b + 2 && q4 < KQ; ++q4) {
+    // the lane group's offset re-derived here (att_planes): no per-row address
+    // kept across the unit loop
+    unsigned goff = (unsigned)g * 16u;
+    asm volatile("" : "+v"(goff));
+    f32x4 rw[NR];
+#pragma unroll
+    for (int n = 0; n < NR; ++n)
+      rw[n] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(RW + (n * KQ + q4) * 16) + goff);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * q4 + e < KS) {
+#pragma unroll
+        for (int n = 0; n < NR; ++n) racc[n][w] = fmaf(rw[n][e], Bx[q4][w][e], racc[n][w]);
+      }
+  }
+}
+// The same GEMM step / block / tile, as the split feed-forward runs: one
+// block's split B operand of one step live (12 VGPRs instead of 36), the NM
+// tiles as independent MFMA chains, the next (block, tile)'s triple read ahead
+// of this one's MFMAs.  Every triple is read once per step: for the phases
+// whose accumulators leave no room for three steps' split operands.  Triple
+// TH (-1: none) is not read here: the caller holds it in wh for the three steps
+// (the one that comes from the global image, read once per unit).
+template <int H, int T0, int NM, int KQ, int KS, int NB, int NMA, int NR, int TH = -1>
+PGP_DEV void att_gemm_steps(f32x4 (&acc)[NMA][3], const float* AL, const float* AG, const f32x4 (&Bx)[NB][3], int lane,
+                            float (&racc)[NR][3], const float* RW, int g, const u32x4 (&wh)[3]) {
+  static_assert(NM <= NMA, "accumulator tiles");
+  constexpr int NBK = cdiv(KQ, 2), NTR = NM * NBK;
+  u32x4 wn[3];
+  att_planes<H>(AL, AG, T0, lane, wn);
+#pragma unroll
+  for (int w = 0; w < 3; ++w) {
+#pragma unroll
+    for (int b = 0; b < NBK; ++b) {
+      u32x4 xb[3];
+      {
+        float v[8];
+        pair_tiles<NB>(Bx, b, w, v);
+        split8(v, xb);
+      }
+      prio_mfma();
+#pragma unroll
+      for (int m = 0; m < NM; ++m) {
+        u32x4 wp[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wp[k] = wn[k];
+        const int q = (b * NM + m + 1) % NTR;
+        if (T0 + q == TH) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) wn[k] = wh[k];
+        } else if (q != 0 || w < 2) {
+          att_planes<H>(AL, AG, T0 + q, lane, wn);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc[m][w] = mfma_bf6(wp, xb, acc[m][w]);
+        if (m == 0) att_rows<KQ, KS, NB, NR>(racc, RW, Bx, b, w, g);
+      }
+      prio_valu();
+    }
+  }
+}
+
+// acc[m][w] += A[m] . B for NM tiles over KQ groups of B k-steps as split-bf16
+// MFMAs, block / tile / step: one block's split B operands of the three steps
+// live (36 VGPRs) and every triple read once per unit, D triples ahead of its
+// MFMAs (att_prologue has read the first D), so that the triples read from the
+// global image cost a unit their bytes once.  The NR VALU rows stay fp32 FMAs on
+// the unsplit B operands, issued beside the first tile's MFMAs.  An accumulator
+// takes its blocks in ascending order whatever the unit.
+template <int H, int T0, int NM, int KQ, int KS, int NB, int NMA, int NR, int D>
+PGP_DEV void att_gemm(f32x4 (&acc)[NMA][3], u32x4 (&wq)[NM * cdiv(KQ, 2)][3], const float* AL, const float* AG,
+                      const f32x4 (&Bx)[NB][3], int lane, float (&racc)[NR][3], const float* RW, int g) {
+  static_assert(NM <= NMA, "accumulator tiles");
+  constexpr int NBK = cdiv(KQ, 2), NTR = NM * NBK;
+#pragma unroll
+  for (int b = 0; b < NBK; ++b) {
+    u32x4 xb[3][3];
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      float v[8];
+      pair_tiles<NB>(Bx, b, w, v);
+      split8(v, xb[w]);
+    }
+    prio_mfma();
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      const int t = b * NM + m;
+      if (t + D < NTR) att_planes<H>(AL, AG, T0 + t + D, lane, wq[t + D]);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int w = 0; w < 3; ++w) {
+        acc[m][w] = mfma_bf6(wq[t], xb[w], acc[m][w]);
+        if (m == 0) att_rows<KQ, KS, NB, NR>(racc, RW, Bx, b, w, g);
+      }
+    }
+    prio_valu();
+  }
+}
 
 // acc[m][w] += A[m] . B for the first NM of NMA accumulator tiles, A = NM tiles
 // x KQ groups in LDS, B k-step s = Bx[s/4][w][s%4]
@@ -329,10 +569,10 @@ PGP_DEV void layer_norm_tiles(f32x4 (&acc)[Geo<H>::MT_D][3], f32x4 (&X)[Geo<H>::
 // Ring state: `cur` holds the stage being computed, `nxt` is being filled.
 // Resident mode: `nxt` is the LDS copy of the whole stream and advance() only
 // moves `cur` to the next stage.
-template <int H, bool SPLIT = false>
+template <int H, bool SPLIT = false, bool AS = false>
 struct Ring {
   using G = Geo<H>;
-  static constexpr bool RES = EncLds<H, SPLIT>::RESIDENT;
+  static constexpr bool RES = EncLds<H, SPLIT, AS>::RESIDENT;
   float* cur;
   float* nxt;
   const float* enc;  // global encoder stream [layer][LAYER_G groups]
@@ -351,7 +591,9 @@ struct Ring {
     if constexpr (RES) {
       const int si = next % (kLayers * G::NST), l = si / G::NST, k = si % G::NST;
       int gi;
-      if constexpr (SPLIT)  // the split image (EncS); layer 0's stages 0, 1 are never read
+      if constexpr (AS)  // EncA: the attention stages address their triples from nxt (att_planes)
+        gi = l == 0 ? EncA<H>::L0F : k == 2 ? EncA<H>::L1F : EncA<H>::L1A;
+      else if constexpr (SPLIT)  // the split image (EncS); layer 0's stages 0, 1 are never read
         gi = l == 0 ? EncS<H>::L0F : k == 2 ? EncS<H>::L1F : EncS<H>::L1A + G::st_begin(k);
       else
         gi = l * G::LAYER_G + G::st_begin(k) - EncLds<H>::RES0;  // < 0: a stage tail mode never reads
@@ -458,12 +700,19 @@ PGP_DEV float row_fold_bias(int m, int n, int w, const float* tab) {
 // Tail-mode layer (Geo<H>::TAIL, H = 50): stages [qk] [v o] [f1 f2].
 // F0: layer 0, q/k/v from the folded raw-feature product (the ring's q/k/v
 // stages are then unused).
-template <int H, bool F0, bool SPLIT>
-PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& ring, const float* TL, int lane,
+// AS: layer 1's q|k, v and out_proj on the split planes too (EncA).
+template <int H, bool F0, bool SPLIT, bool AS = false>
+PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT, AS>& ring, const float* TL, int lane,
                                 const float* tab, const float (&ba)[3], const float (&xv)[3][3]) {
   using G = Geo<H>;
   constexpr int TQ = G::TQ, SR = G::SR, HF = G::HF;
   const int g = lane >> 4;
+  // (AS) the attention triples' LDS and global images, and how far ahead the
+  // block-outer GEMMs read them
+  using EA = EncA<H>;
+  constexpr int kAhead = 1;
+  const float* AL = ring.nxt + EA::L1A * G::FQ;
+  const float* AG = ring.enc + EA::L1A * G::FQ;
   // [S0] q and k of both heads
   constexpr bool BIL = F0;  // layer 0's scores as bilinear forms (the q / k fold is not needed)
   f32x4 QK[BIL ? 1 : 2 * TQ][3];
@@ -478,7 +727,16 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
     }
     float qkr[2 * SR][3];
     zero_rows(qkr);
-    gemm3_rows<2 * TQ, G::KQ_D, G::KS_D, G::MT_D, 2 * TQ, 2 * SR>(QK, ring.cur, X, lane, qkr, TL + G::TL_RQ, g);
+    if constexpr (AS) {
+      // step by step (QK's 72 accumulator VGPRs leave no room for three steps'
+      // split X); all of q|k's triples are LDS-resident
+      static_assert(EA::TQK <= EA::NRES, "q|k triples in LDS");
+      const u32x4 none[3] = {};
+      att_gemm_steps<H, 0, 2 * TQ, G::KQ_D, G::KS_D, G::MT_D, 2 * TQ, 2 * SR>(QK, AL, AG, X, lane, qkr,
+                                                                            TL + G::TL_RQ, g, none);
+    } else {
+      gemm3_rows<2 * TQ, G::KQ_D, G::KS_D, G::MT_D, 2 * TQ, 2 * SR>(QK, ring.cur, X, lane, qkr, TL + G::TL_RQ, g);
+    }
     rows_finish(qkr);
 #pragma unroll
     for (int n = 0; n < SR; ++n)
@@ -489,6 +747,14 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
       }
   }
   ring.advance();
+  // (AS, layer 1) v's triple of the global image: read here, once per unit, a
+  // softmax ahead of its MFMAs, and held for the three steps
+  u32x4 vh[3] = {};
+  if constexpr (AS && !F0) {
+    static_assert(EA::NRES == EA::TQK + EA::TV - 1, "one v triple in the global image");
+    att_planes<H>(AL, AG, EA::NRES, lane, vh);
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // scores of both heads; the shared tile's slot 4r+g belongs to head 0 below HT
   float P0[3][3], P1[3][3];
   if constexpr (BIL) {
@@ -564,6 +830,9 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
     P1[w][2] = e12 * i1;
   }
   f32x4 acc[G::MT_D][3];
+  // (AS, layer 1) formed after the v GEMM instead: its read-ahead is pinned by
+  // scheduling barriers, which would keep these 48 VGPRs live across it
+  if constexpr (F0 || !AS) {
 #pragma unroll
   for (int mt = 0; mt < G::MT_D; ++mt) {
     const f32x4 bo = ld4(TL + G::TL_BO + 16 * mt + 4 * g);
@@ -575,6 +844,7 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
 #pragma unroll
       for (int w = 0; w < 3; ++w) acc[mt][w] = X[mt][w] * g0 + bo;
     }
+  }
   }
   if constexpr (F0) {
     // [S1] layer 0: out_proj through the attention, folded (no v, no P.v):
@@ -612,8 +882,27 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
     for (int w = 0; w < 3; ++w) V[t][w] = bias;
   }
   zero_rows(vr);
-  gemm3_rows<TQ, G::KQ_D, G::KS_D, G::MT_D, TQ, SR>(V, ring.cur, X, lane, vr, TL + G::TL_RQ + 2 * SR * G::KQ_D * 16,
-                                                         g);
+  if constexpr (AS) {
+    // step by step too (X, the scores and V live); its last triple, the one
+    // that comes from the global image, was read above the scores (vh)
+    att_gemm_steps<H, EA::TQK, TQ, G::KQ_D, G::KS_D, G::MT_D, TQ, SR, EA::NRES>(
+        V, AL, AG, X, lane, vr, TL + G::TL_RQ + 2 * SR * G::KQ_D * 16, g, vh);
+  } else {
+    gemm3_rows<TQ, G::KQ_D, G::KS_D, G::MT_D, TQ, SR>(V, ring.cur, X, lane, vr, TL + G::TL_RQ + 2 * SR * G::KQ_D * 16,
+                                                      g);
+  }
+  // (AS) out_proj's first triples come from the global image: read above P.v
+  u32x4 wo[AS ? EA::TO : 1][3];
+  if constexpr (AS) {
+    att_prologue<H, EA::TQK + EA::TV, EA::TO, kAhead>(AL, AG, lane, wo);
+#pragma unroll
+    for (int mt = 0; mt < G::MT_D; ++mt) {
+      const f32x4 bo = ld4(TL + G::TL_BO + 16 * mt + 4 * g);
+      const f32x4 g0 = ld4(TL - G::TL_SIZE + G::TL_LN2G + 16 * mt + 4 * g);
+#pragma unroll
+      for (int w = 0; w < 3; ++w) acc[mt][w] = X[mt][w] * g0 + bo;
+    }
+  }
   // v row n (+ its bias) in lane group n, 0 in groups >= SR (the bias table is
   // padded to 8 entries, so slot 2*SR + g is in bounds)
   float vd[3];
@@ -642,8 +931,12 @@ PGP_DEV void encoder_layer_tail(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H, SPLIT>& rin
   {
     float ro[G::XR][3];
     zero_rows(ro);
-    gemm3_rows<G::MT_X, G::KQ_OT, G::KS_OT, TQ + 1, G::MT_D, G::XR>(acc, ring.cur + G::G_V * G::FQ, O, lane, ro,
-                                                                   TL + G::TL_RO, g);
+    if constexpr (AS)
+      att_gemm<H, EA::TQK + EA::TV, G::MT_X, G::KQ_OT, G::KS_OT, TQ + 1, G::MT_D, G::XR, kAhead>(
+          acc, wo, AL, AG, O, lane, ro, TL + G::TL_RO, g);
+    else
+      gemm3_rows<G::MT_X, G::KQ_OT, G::KS_OT, TQ + 1, G::MT_D, G::XR>(acc, ring.cur + G::G_V * G::FQ, O, lane, ro,
+                                                                     TL + G::TL_RO, g);
 #pragma unroll
     for (int w = 0; w < 3; ++w) acc[G::MT_X][w][0] += rows_pick<G::XR>(ro, w);
   }
@@ -909,159 +1202,38 @@ PGP_DEV void encoder_layer(f32x4 (&X)[Geo<H>::MT_D][3], Ring<H>& ring, const flo
 template <int H, bool SPLIT>
 __global__ __launch_bounds__(enc_waves<H>() * 64, H <= 16 ? kEnc16EU : tail_res<H>() ? 1 : 2) void encoder_kernel(
     FwdArgs a) {
-  using G = Geo<H>;
+  constexpr bool AS = false;
   using L = EncLds<H, SPLIT>;
   __shared__ __attribute__((aligned(16))) float smem[L::TOTAL];
   // tail-resident mode: per-wave staging slot of the next unit's raw features
   __shared__ float xstage[L::UNITS ? NW_STAGE<H>() * 144 : 1];
-  float* tab = smem + (L::RESIDENT ? L::STREAM : 2 * L::SLOT);
-  const int tsz = G::t_size(a.K);
-  for (int i = threadIdx.x; i < tsz; i += blockDim.x) tab[i] = a.tab[i];
-
-  const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr int NW = enc_waves<H>();
-  const long nblk = (a.B + 15) / 16;
-
-  Ring<H, SPLIT> ring{smem, smem + L::SLOT, a.frags + G::OFF_ENC, 0, H * kLayers * G::NST, wv, lane};
-  if constexpr (SPLIT) {
-    dma_groups(a.encb, smem, EncS<H>::GROUPS, wv, NW, lane);
-    ring.nxt = smem;
-    ring.next = 1;
-    __syncthreads();
-  } else if constexpr (L::RESIDENT) {
-    dma_groups(a.frags + G::OFF_ENC + (long)L::RES0 * G::FQ, smem, kLayers * G::LAYER_G - L::RES0, wv, NW, lane);
-    ring.nxt = smem;
-    ring.next = 1;
-    __syncthreads();
-  } else {
-    ring.nxt = smem;  // prologue: stage 0 -> slot 0
-    ring.issue();
-    ring.nxt = smem + L::SLOT;
-    ring.next = 1;
-    __syncthreads();
-    ring.issue();  // stage 1 -> slot 1
-  }
-
-  // one (16-window block, host) unit: hosts are independent in the encoder
-  // one (16-window block, host) unit: hosts are independent in the encoder.
-  // tail-resident mode: pre = the unit's 144 raw-feature floats ([step][feature]
-  // [window], the agg layout) staged in LDS by the caller; otherwise loaded here
-  auto unit = [&](long blk, int h, bool active, const float* pre) {
-    const float* agg = a.agg + (active ? blk : 0) * H * 3 * 48;
-    float* lat = a.lat + (active ? blk : 0) * G::LAT_BLK;
-    float ba[3];
-    // all 3 raw features of every step of this lane's window (layer 0's bilinear scores)
-    float xv[3][3];
-    if constexpr (L::UNITS) {
-#pragma unroll
-      for (int w = 0; w < 3; ++w) {
-#pragma unroll
-        for (int f = 0; f < 3; ++f) xv[w][f] = G::TAIL ? pre[w * 48 + 16 * f + j] : 0.f;
-        const float v = pre[w * 48 + (lane < 48 ? lane : 47)];
-        ba[w] = g < 3 ? v : 0.f;  // feature g of window j
-      }
-    } else {
-#pragma unroll
-      for (int w = 0; w < 3; ++w) ba[w] = (active && g < 3) ? agg[(h * 3 + w) * 48 + lane] : 0.f;
-#pragma unroll
-      for (int w = 0; w < 3; ++w)
-#pragma unroll
-        for (int f = 0; f < 3; ++f)
-          xv[w][f] = (G::TAIL && active) ? agg[(h * 3 + w) * 48 + 16 * f + j] : 0.f;
-    }
-    f32x4 X[G::MT_D][3];
-#pragma unroll
-    for (int mt = 0; mt < G::MT_D; ++mt) {
-      const float aw = tab[G::T_TEW + mt * 64 + lane];
-#pragma unroll
-      for (int w = 0; w < 3; ++w) X[mt][w] = mfma(aw, ba[w], ld4(tab + G::T_TE + w * G::DP + 16 * mt + 4 * g));
-    }
-    static_assert(kLayers == 2, "layer 0 (folded q/k/v) + layer 1");
-    if constexpr (G::TAIL) {
-      encoder_layer_tail<H, true, SPLIT>(X, ring, tab + G::T_L0, lane, tab, ba, xv);
-      encoder_layer_tail<H, false, SPLIT>(X, ring, tab + G::T_L0 + G::TL_SIZE, lane, tab, ba, xv);
-    } else if constexpr (!SPLIT) {
-      encoder_layer<H, true>(X, ring, tab + G::T_L0, lane, tab, ba);
-      encoder_layer<H, false>(X, ring, tab + G::T_L0 + G::TL_SIZE, lane, tab, ba);
-    }
-
-    if (active) {
-#pragma unroll
-      for (int w = 0; w < 3; ++w) {
-        // chunk (h, w): full groups of 4 k-steps as one 16-byte store per lane,
-        // the remaining k-steps one dword each (pgp_layout.hpp, LAT_FG)
-        float* lc = lat + (long)((h * 3 + w) * G::KS_D) * 64;
-#pragma unroll
-        for (int q = 0; q < G::LAT_FG; ++q) *reinterpret_cast<f32x4*>(lc + q * 256 + lane * 4) = X[q][w];
-        if constexpr (G::KS_D % 4 != 0) {
-#pragma unroll
-          for (int r = 0; r < G::KS_D % 4; ++r) lc[G::LAT_FG * 256 + r * 64 + lane] = X[G::LAT_FG][w][r];
-        }
-      }
-      if (a.latent != nullptr) {
-        const long b = blk * 16 + j;
-        if (b < a.B) {
-#pragma unroll
-          for (int w = 0; w < 3; ++w)
-#pragma unroll
-            for (int mt = 0; mt < G::MT_D; ++mt)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int c = 16 * mt + 4 * r + g;
-                const float* TL1 = tab + G::T_L0 + G::TL_SIZE;  // the latent = gamma * x-hat + beta
-                if (c < H)
-                  a.latent[b * G::LAT + (long)h * 3 * H + w * H + c] =
-                      X[mt][w][r] * TL1[G::TL_LN2G + 16 * mt + 4 * g + r] + TL1[G::TL_LN2B + 16 * mt + 4 * g + r];
-              }
-        }
-      }
-    }
-  };
-  if constexpr (L::UNITS) {
-    // no barrier in the host loop: each wave takes an equal contiguous range of
-    // the nblk x H units (grid = the workgroups that fit at once: CU count x
-    // occupancy), so the launch has no partial last round of workgroups
-    const long U = nblk * H, NWT = (long)gridDim.x * NW, gw = (long)blockIdx.x * NW + wv;
-    const long u1 = (gw + 1) * U / NWT;
-    // unit u's raw features are agg[u * 144 ..] (144 floats).  The next unit's
-    // are loaded while this one computes and staged through a per-wave LDS slot
-    // after this unit's latent stores: no loop-carried registers, so the wait
-    // for them is a counted vmcnt in the body (long satisfied) instead of a
-    // vmcnt(0) at the loop head that would also wait for the stores.
-    float* slot = xstage + wv * 144;
-    const long u0 = gw * U / NWT;
-    float pf[3];
-    auto load_x = [&](long u) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) pf[k] = a.agg[u * 144 + (64 * k + lane < 144 ? 64 * k + lane : 143)];
-    };
-    auto stage_x = [&]() {
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (64 * k + lane < 144) slot[64 * k + lane] = pf[k];
-    };
-    if (u0 < u1) {
-      load_x(u0);
-      stage_x();
-    }
-#pragma unroll 1
-    for (long u = u0; u < u1; ++u) {
-      load_x(u + 1 < u1 ? u + 1 : u);
-      const long blk = u / H;
-      unit(blk, (int)(u - blk * H), true, slot);
-      stage_x();
-    }
-  } else {
-    const long blk = (long)blockIdx.x * NW + wv;
-    const bool active = blk < nblk;  // inactive waves still take part in the ring and barriers
-#pragma unroll 1
-    for (int h = 0; h < H; ++h) unit(blk, h, active, nullptr);
-  }
+#include "pgp_encoder_body.inc"
 }
 
-template <int H, bool SPLIT>
+// The attention-split form (H = 50): the split feed-forward, and layer 1's
+// attention projections on split planes of which the last ones are read from
+// the global image (EncA).  A kernel of its own beside encoder_kernel<H, true>.
+template <int H>
+__global__ __launch_bounds__(enc_waves<H>() * 64, 1) void encoder_asplit_kernel(FwdArgs a) {
+  static_assert(enc_asplit<H>(), "LDS budget of the attention-split form");
+  constexpr bool SPLIT = true, AS = true;
+  using L = EncLds<H, true, true>;
+  __shared__ __attribute__((aligned(16))) float smem[L::TOTAL];
+  __shared__ float xstage[NW_STAGE<H>() * 144];
+#include "pgp_encoder_body.inc"
+}
+
+template <int H, bool SPLIT, bool AS>
+auto enc_kernel_ptr() {
+  if constexpr (AS)
+    return &encoder_asplit_kernel<H>;
+  else
+    return &encoder_kernel<H, SPLIT>;
+}
+
+template <int H, bool SPLIT, bool AS = false>
 hipError_t launch_form(const FwdArgs& a, hipStream_t st) {
+  const auto kern = enc_kernel_ptr<H, SPLIT, AS>();
   const long nblk = (a.B + 15) / 16;
   constexpr int NW = enc_waves<H>();
   long grid = (nblk + NW - 1) / NW;
@@ -1072,7 +1244,7 @@ hipError_t launch_form(const FwdArgs& a, hipStream_t st) {
   static std::atomic<int> fits{-1};
   if (fits.load(std::memory_order_relaxed) < 0) {
     hipFuncAttributes fa{};
-    const bool ok = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(encoder_kernel<H, SPLIT>)) == hipSuccess &&
+    const bool ok = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) == hipSuccess &&
                     fa.maxThreadsPerBlock >= NW * 64;
     fits.store(ok ? 1 : 0, std::memory_order_relaxed);
   }
@@ -1081,19 +1253,20 @@ hipError_t launch_form(const FwdArgs& a, hipStream_t st) {
     static std::atomic<int> occ_cache{0};  // workgroups resident per CU (registers / LDS), queried once
     int occ = occ_cache.load(std::memory_order_relaxed);
     if (occ <= 0) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, encoder_kernel<H, SPLIT>, NW * 64, 0) != hipSuccess ||
-          occ <= 0)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NW * 64, 0) != hipSuccess || occ <= 0)
         occ = 1;
       occ_cache.store(occ, std::memory_order_relaxed);
     }
     grid = std::min<long>((long)device_cus() * occ, (nblk * H + NW - 1) / NW);
   }
-  encoder_kernel<H, SPLIT><<<(int)grid, NW * 64, 0, st>>>(a);
+  kern<<<(int)grid, NW * 64, 0, st>>>(a);
   return hipGetLastError();
 }
 
 template <int H>
 hipError_t launch(const FwdArgs& a, hipStream_t st) {
+  if constexpr (enc_asplit<H>())
+    if (a.encb != nullptr && a.enc_form == 1) return launch_form<H, true, true>(a, st);
   if constexpr (enc_split<H>())
     if (a.encb != nullptr) return launch_form<H, true>(a, st);
   return launch_form<H, false>(a, st);
@@ -1105,6 +1278,10 @@ hipError_t launch_split(const float* frags, float* encb, hipStream_t st) {
     using G = Geo<H>;
     constexpr long n = 2L * (G::MT_F * EncS<H>::NBD + G::MT_X * EncS<H>::NBF) + G::P_F1;
     enc_split_kernel<H><<<(int)((n + 3) / 4), 256, 0, st>>>(frags + G::OFF_ENC, encb);
+    if constexpr (enc_asplit<H>()) {  // the attention-split image follows
+      constexpr long na = 2L * (G::MT_F * EncS<H>::NBD + G::MT_X * EncS<H>::NBF) + EncA<H>::NT;
+      enc_asplit_kernel<H><<<(int)((na + 3) / 4), 256, 0, st>>>(frags + G::OFF_ENC, encb + EncS<H>::SIZE);
+    }
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
@@ -1127,11 +1304,38 @@ long encoder_split_floats(int H) {
   switch (H) {
 #define CASE(h) \
   case h:       \
-    return enc_split<h>() ? EncS<h>::SIZE : 0;
+    return enc_split<h>() ? EncS<h>::SIZE + (enc_asplit<h>() ? EncA<h>::SIZE : 0) : 0;
     PGP_FOR_EACH_H(CASE)
 #undef CASE
   }
   return 0;
+}
+
+bool encoder_asplit(int H) {
+  switch (H) {
+#define CASE(h) \
+  case h:       \
+    return enc_asplit<h>();
+    PGP_FOR_EACH_H(CASE)
+#undef CASE
+  }
+  return false;
+}
+
+void encoder_asplit_geometry(int H, int* lds_bytes, int* resident, int* streamed) {
+  *lds_bytes = *resident = *streamed = 0;
+  switch (H) {
+#define CASE(h)                                      \
+  case h:                                            \
+    if (enc_asplit<h>()) {                           \
+      *lds_bytes = enc_asplit_lds_bytes<h>();        \
+      *resident = EncA<h>::NRES;                     \
+      *streamed = EncA<h>::NT - EncA<h>::NRES;       \
+    }                                                \
+    return;
+    PGP_FOR_EACH_H(CASE)
+#undef CASE
+  }
 }
 
 hipError_t launch_encoder_split(int H, const float* frags, float* encb, hipStream_t st) {

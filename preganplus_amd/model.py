@@ -89,10 +89,12 @@ class DecisionModel:
         on the fp32 MFMA (False); ``pgp_gan_split``."""
         _native.check(self._L.pgp_gan_split(self._h, int(bool(on))), "pgp_gan_split")
 
-    def encoder_split(self, on: bool):
-        """K2's feed-forward on split-bf16 MFMAs (True: the default where
-        compiled, H = 50) or on the fp32 MFMA (False); ``pgp_encoder_split``."""
-        _native.check(self._L.pgp_encoder_split(self._h, int(bool(on))), "pgp_encoder_split")
+    def encoder_split(self, on):
+        """K2's form (H = 50; ``pgp_encoder_split``): 0 / False = the fp32 MFMA
+        throughout; 1 / True = the best split form compiled, the default (the
+        feed-forward and layer 1's attention projections on split-bf16 MFMAs);
+        2 = the feed-forward alone on split-bf16 MFMAs."""
+        _native.check(self._L.pgp_encoder_split(self._h, int(on)), "pgp_encoder_split")
 
     def decoder_split(self, on: bool):
         """K2b on split-bf16 MFMAs (True: the default where compiled, H = 32 and

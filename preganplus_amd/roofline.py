@@ -73,9 +73,18 @@ def encoder_split(H: int) -> bool:
     return H in ENC_SPLIT_MFMA_PER_HOST
 
 
+# The attention-split form (pgp_encoder.hip EncA, encoder_asplit_kernel<H>, the
+# default where compiled): layer 1's q|k, v and out_proj on split planes too:
+# 468 fp32 MFMAs fewer, 12 tiles x 2 blocks x 6 products x 3 steps bf16 more
+# (tools/isa_count.py encoder_asplit_counts).
+ENC_ASPLIT_MFMA_PER_HOST = {50: (48, 936)}
+
+
 def encoder_split_executed_flops_per_window(H: int):
-    """(fp32 MFMA flops, bf16 MFMA flops) K2's split form executes per window."""
-    f32, bf = ENC_SPLIT_MFMA_PER_HOST[H]
+    """(fp32 MFMA flops, bf16 MFMA flops) K2's default split form executes per
+    window: the attention-split form's where compiled, else the split
+    feed-forward's."""
+    f32, bf = ENC_ASPLIT_MFMA_PER_HOST.get(H) or ENC_SPLIT_MFMA_PER_HOST[H]
     return f32 * 2048 * H / 16, bf * 16 * 16 * 32 * 2 * H / 16
 
 

@@ -86,6 +86,23 @@ def encoder_split_counts(Hs=(50,), lib=LIB):
     return out
 
 
+def encoder_asplit_counts(Hs=(50,), lib=LIB):
+    """{H: (f32 16x16x4 MFMAs, bf16 16x16x32 MFMAs, other VALU)} per host and
+    wave of the attention-split form encoder_asplit_kernel<H>."""
+    asm = _disasm(lib, "encoder_asplit_kernel")
+    out = {}
+    for H in Hs:
+        m = re.search(rf"<_ZN3pgp12_GLOBAL__N_121encoder_asplit_kernelILi{H}EEEvNS_7FwdArgsE>:\n(.*?)s_endpgm", asm, re.S)
+        if m is None:
+            raise RuntimeError(f"encoder_asplit_kernel<{H}> not found in {lib}")
+        body = m.group(1)
+        f32 = len(re.findall(r"^\s+v_mfma_f32_16x16x4", body, re.M))
+        bf = len(re.findall(r"^\s+v_mfma_f32_16x16x32_bf16", body, re.M))
+        valu = len(re.findall(r"^\s+v_", body, re.M)) - len(re.findall(r"^\s+v_mfma", body, re.M))
+        out[H] = (f32, bf, valu)
+    return out
+
+
 _ASM_CACHE = {}
 
 
@@ -132,6 +149,8 @@ if __name__ == "__main__":
         print(f"H={H}: {mfma} MFMA (16x16x4 f32), {valu} other VALU per host and wave")
     for H, (f32, bf, valu) in encoder_split_counts([h for h in Hs if h == 50]).items():
         print(f"H={H} split FFN: {f32} MFMA 16x16x4 f32 + {bf} MFMA 16x16x32 bf16, {valu} other VALU per host and wave")
+    for H, (f32, bf, valu) in encoder_asplit_counts([h for h in Hs if h == 50]).items():
+        print(f"H={H} split FFN + layer-1 attention: {f32} MFMA 16x16x4 f32 + {bf} MFMA 16x16x32 bf16, {valu} other VALU per host and wave")
     for H, d in tune_counts(Hs).items():
         print(f"H={H}: fused tuning kernels, MFMA per unit: {d}")
 
