@@ -416,6 +416,56 @@ int pgp_tune_forward_many(int n_hosts, int n_windows, const float* windows, cons
 int pgp_forward1(int n_hosts, int n_protos, const float* window, const float* sched, const float* P,
                  const double* prototypes_device, float* logits, float* protos, int* cls, int* any_anom, float* probs,
                  int* keep_orig, int* final_target, int* gen_target, void* stream);
+/* ---- a fleet of cells, each on its own weights (n_hosts 8 or 16) ----
+ * The reference keeps one decision model per environment: every
+ * PreGANPlusRecovery owns its Transformer_16 and tunes it each interval on its
+ * own last ten windows (recovery/PreGANPlus.py:51-58,
+ * recovery/PreGANSrc/src/train.py:42-57, 94-109).  These entries run the
+ * fused batch-1 step, accuracy()'s forward and the per-interval forward for
+ * n_cells such models in ONE launch each: workgroup b is cell b and works on
+ * slot b of every per-cell array.  All arrays are device memory, per-cell
+ * arrays are contiguous slots:
+ *   P, G, exp_avg, exp_avg_sq  [n_cells][pgp_master_len(H)]
+ *   state                      [n_cells][2K+3] fp64 (as pgp_tune_targets)
+ *   windows                    [n_cells][n_steps][3][3H]
+ *   y, cls                     [n_cells][n_steps][H] int32
+ *   loss                       [n_cells][n_steps][2] fp64
+ *   logits, protos             [n_cells][H][2]   (the step's own outputs)
+ *   rng                        [n_cells][2] u64 = {seed, base step} per cell
+ *   active                     [n_cells] int32, or NULL: every cell
+ * A cell whose active entry is 0 reads and writes nothing of its slot.  The
+ * slots are disjoint and no workgroup waits for another; the step holds one
+ * CU per cell, more cells than CUs queue.  Cell m's results have the bits the
+ * single-cell entry gives on slot m's arrays, whatever n_cells and the other
+ * cells are.
+ * Errors are returned before anything is enqueued: PGP_ERR_UNSUPPORTED for a
+ * host count other than 8 / 16; PGP_ERR_ARG for a negative count, a step
+ * outside [0, n_steps), p outside [0, 1) or a NULL array with n_cells > 0.
+ * n_cells == 0 is PGP_OK and launches nothing.
+ *
+ * pgp_tune_step1_many: step `step` of every active cell's backprop
+ * (train.py:46-53) on window [m][step]: pgp_tune_step1 on slot m, or with
+ * p > 0 pgp_tune_step1_dropout with rng[m] and the same `step`.  p == 0
+ * launches the step without dropout and leaves rng unread. */
+int pgp_tune_step1_many(int n_hosts, int n_protos, int n_cells, int n_steps, int step, const int* active,
+                        const float* windows, const int* y, const int* cls, const float* P, float* G, double* state,
+                        double update_min, double decay, float* logits, float* protos, double* loss, float p,
+                        const unsigned long long* rng, void* stream);
+/* pgp_tune_forward_many per cell on its own slot of P (accuracy()'s forward,
+ * train.py:94-109): windows [n_cells][n_windows][3][3H]; logits64 / protos64
+ * [n_cells][n_windows][H][2] fp64.  At most 65535 cells. */
+int pgp_tune_forward_cells(int n_hosts, int n_cells, int n_windows, const int* active, const float* windows,
+                           const float* P, double* logits64, double* protos64, void* stream);
+/* pgp_forward1 per cell (run_model, PreGANPlus.py:115-136, of each
+ * environment's own model): windows [n_cells][3][3H], sched [n_cells][H][H];
+ * the prototypes are the first 2K doubles of the cell's state slot, the GAN
+ * weights the cell's own gen / disc sections of P.  Outputs as pgp_forward1
+ * with a leading n_cells axis: logits / protos [n_cells][H][2], cls
+ * [n_cells][H], any_anom [n_cells], probs [n_cells][2], keep_orig [n_cells],
+ * final_target / gen_target [n_cells][H]. */
+int pgp_forward1_many(int n_hosts, int n_protos, int n_cells, const int* active, const float* windows,
+                      const float* sched, const float* P, const double* state, float* logits, float* protos, int* cls,
+                      int* any_anom, float* probs, int* keep_orig, int* final_target, int* gen_target, void* stream);
 /* ---- data-parallel tuning step on the device ----
  * pgp_tune_dataset replaces load_on_the_fly_dataset (utils.py:40-47) for a
  * batch of E environments: series [E,R,3H] fp64 = each environment's last R
@@ -484,6 +534,20 @@ int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float
 int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
                     float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors,
                     const float* sched, void* stream);
+/* pgp_adamw_table on every active slot of a fleet in one launch (each cell's
+ * own torch.optim.AdamW, utils.py:65, stepped after its own backward,
+ * recovery/PreGANSrc/src/train.py:51-54): P / G / exp_avg / exp_avg_sq
+ * [n_cells][slot_len] floats, tensor offsets relative to the slot (inside
+ * [0, slot_len)), cell c's table at sched + c * sched_cell_stride floats
+ * ([ntensors][3] as above).  active [n_cells] int32 or NULL; an inactive
+ * cell's slot is neither read nor written.  The same bits as pgp_adamw_table
+ * on that slot.  At most 65535 cells; PGP_ERR_ARG before anything is enqueued
+ * for a negative count, a tensor outside the slot or a NULL array with
+ * n_cells > 0; n_cells == 0 is PGP_OK. */
+int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, float* P, const float* G, float* exp_avg,
+                         float* exp_avg_sq, float lr, float weight_decay, float beta1, float beta2, float eps,
+                         const pgp_adam_tensor* tensors, int ntensors, const float* sched,
+                         long long sched_cell_stride, void* stream);
 
 /* train_gan (PreGANPlus.py:60-81) for ONE window in two launches, n_hosts 8 or
  * 16 (the plugin's per-interval call), replacing pgp_gan_forward +

@@ -696,6 +696,57 @@ int pgp_forward1(int n_hosts, int n_protos, const float* window, const float* sc
   return PGP_OK;
 }
 
+// ---- a fleet of cells, each on its own weights (recovery/PreGANPlus.py:51-58: one Transformer_16 per
+// PreGANPlusRecovery, tuned on its own windows, recovery/PreGANSrc/src/train.py:42-57, 94-109) ----
+// Every check runs before anything is enqueued: a refused call launches nothing.
+int pgp_tune_step1_many(int n_hosts, int n_protos, int n_cells, int n_steps, int step, const int* active,
+                        const float* windows, const int* y, const int* cls, const float* P, float* G, double* state,
+                        double update_min, double decay, float* logits, float* protos, double* loss, float p,
+                        const unsigned long long* rng, void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (fused step for a fleet: 8 or 16)");
+  unsigned int thr = 0;
+  if (!drop_threshold(p, &thr)) return fail(PGP_ERR_ARG, "dropout p outside [0, 1)");
+  if (n_protos < 3) return fail(PGP_ERR_ARG, "triplet_loss needs prototypes 0-2");
+  if (n_cells < 0 || n_steps < 0) return fail(PGP_ERR_ARG, "n_cells >= 0, n_steps >= 0");
+  if (step < 0 || step >= n_steps) return fail(PGP_ERR_ARG, "step outside [0, n_steps)");
+  if (n_cells == 0) return PGP_OK;
+  if (!windows || !y || !cls || !P || !G || !state || !logits || !protos || !loss)
+    return fail(PGP_ERR_ARG, "bad tune_step1_many arguments");
+  if (thr && !rng) return fail(PGP_ERR_ARG, "dropout needs rng = {seed, base step} per cell");
+  HIPCHK(launch_tune1_cells(n_hosts, n_protos, n_cells, n_steps, step, active, windows, y, cls, P, G, state,
+                            update_min, decay, logits, protos, loss, thr, thr ? 1.0f / (1.0f - p) : 1.f, rng,
+                            reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_tune_forward_cells(int n_hosts, int n_cells, int n_windows, const int* active, const float* windows,
+                           const float* P, double* logits, double* protos, void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (fused forward for a fleet: 8 or 16)");
+  if (n_cells < 0 || n_windows < 0) return fail(PGP_ERR_ARG, "n_cells >= 0, n_windows >= 0");
+  if (n_cells > kMaxFwdCells) return fail(PGP_ERR_ARG, "n_cells above 65535 (one grid row per cell)");
+  if (n_cells == 0 || n_windows == 0) return PGP_OK;
+  if (!windows || !P || !logits || !protos) return fail(PGP_ERR_ARG, "bad tune_forward_cells arguments");
+  HIPCHK(launch_fwd_cells(n_hosts, n_cells, n_windows, active, windows, P, logits, protos,
+                          reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_forward1_many(int n_hosts, int n_protos, int n_cells, const int* active, const float* windows,
+                      const float* sched, const float* P, const double* state, float* logits, float* protos, int* cls,
+                      int* any_anom, float* probs, int* keep_orig, int* final_target, int* gen_target, void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (batch-1 forward for a fleet: 8 or 16)");
+  if (n_protos < 1 || n_protos > kMaxProtos) return fail(PGP_ERR_ARG, "n_protos out of range");
+  if (n_cells < 0) return fail(PGP_ERR_ARG, "n_cells >= 0");
+  if (n_cells == 0) return PGP_OK;
+  if (!windows || !sched || !P || !state || !logits || !protos || !cls || !any_anom || !probs || !keep_orig ||
+      !final_target || !gen_target)
+    return fail(PGP_ERR_ARG, "bad forward1_many arguments");
+  HIPCHK(launch_infer1_cells(n_hosts, n_protos, n_cells, active, windows, sched, P, state, logits, protos, cls,
+                             any_anom, probs, keep_orig, final_target, gen_target,
+                             reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
 int pgp_tune_dataset(int n_hosts, int n_env, int n_rows, const double* series, const double* train_max,
                      float* windows, int* y, int* cls, float* infer, void* stream) {
   if (n_hosts <= 0 || n_hosts > 64) return fail(PGP_ERR_UNSUPPORTED, "host count");
@@ -888,6 +939,42 @@ int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq,
     a.t[i].bc2_sqrt = tensors[i].bc2_sqrt;
   }
   HIPCHK(launch_adamw(a, reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+// pgp_adamw_table on every active slot of a fleet (each cell its own optimizer, utils.py:65, stepped after its
+// own backward, recovery/PreGANSrc/src/train.py:51-54)
+int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, float* P, const float* G, float* exp_avg,
+                         float* exp_avg_sq, float lr, float weight_decay, float beta1, float beta2, float eps,
+                         const pgp_adam_tensor* tensors, int ntensors, const float* sched,
+                         long long sched_cell_stride, void* stream) {
+  if (n_cells < 0 || ntensors < 0 || ntensors > kMaxTensors || slot_len < 0 || sched_cell_stride < 0)
+    return fail(PGP_ERR_ARG, "bad adamw_table_many counts");
+  if (n_cells > 65535) return fail(PGP_ERR_ARG, "n_cells above 65535 (one grid row per cell)");
+  if (n_cells == 0) return PGP_OK;
+  if (!P || !G || !exp_avg || !exp_avg_sq || !sched || (ntensors > 0 && !tensors))
+    return fail(PGP_ERR_ARG, "bad adamw_table_many arguments");
+  if (ntensors == 0) return PGP_OK;
+  AdamArgs a{};
+  a.param = P;
+  a.grad = const_cast<float*>(G);
+  a.m = exp_avg;
+  a.v = exp_avg_sq;
+  a.lr_wd = lr * weight_decay;
+  a.b1 = beta1;
+  a.b2 = beta2;
+  a.eps = eps;
+  a.ntensors = ntensors;
+  a.sched = sched;
+  for (int i = 0; i < ntensors; ++i) {
+    if (tensors[i].offset < 0 || tensors[i].n < 0 || tensors[i].offset + tensors[i].n > slot_len)
+      return fail(PGP_ERR_ARG, "AdamW tensor outside the slot");
+    a.t[i].off = (long)tensors[i].offset;
+    a.t[i].n = tensors[i].n;
+    a.t[i].active = kAdamFromTable;  // every row from the cell's table
+  }
+  HIPCHK(launch_adamw_cells(a, n_cells, (long)slot_len, active, (long)sched_cell_stride,
+                            reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;
 }
 

@@ -139,6 +139,10 @@ struct AdamFuse;
 long gan_workspace_floats(int H, int B);
 int gan_plan_slices(int H, int B);  // k-slices of the GAN step (pgp_gan_plan_info); 0: H not compiled
 hipError_t launch_adamw(const AdamArgs& a, hipStream_t st);
+// the same update on slot c of n_cells contiguous slots (a's pointers name slot 0, slot_len floats each), each
+// cell with the table row a.sched + c * sched_cell_stride; active [n_cells] or NULL (pgp_adamw_table_many)
+hipError_t launch_adamw_cells(const AdamArgs& a, int n_cells, long slot_len, const int* active,
+                              long sched_cell_stride, hipStream_t st);
 // fused batch-1 GAN step (pgp_gan1.hip), H in {8, 16}
 bool gan1_supported(int H);
 hipError_t launch_gan1_forward(int H, const float* emb, const float* sched, const float* Pg, const float* Pd,

@@ -45,6 +45,34 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, AdamGrid g) {
   }
 }
 
+// The table-driven update for a fleet of cells (pgp_adamw_table_many): grid
+// (blocks of one slot, cells).  Cell c = blockIdx.y updates slot c of the four
+// buffers (slot_len floats each, offsets in 64 bits) with its own table row
+// a.sched + c * sched_stride; an inactive cell leaves before it reads anything
+// of its slot.  Per element the same adamw_update as adamw_kernel.
+__global__ __launch_bounds__(256) void adamw_cells_kernel(AdamArgs a, AdamGrid g, const int* __restrict__ active,
+                                                          long slot_len, long sched_stride) {
+  const long c = blockIdx.y;
+  if (active && !active[c]) return;
+  const int bx = blockIdx.x;
+  int lo = 0, hi = a.ntensors - 1;  // the last tensor whose first block is <= bx
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (bx >= g.bx0[mid]) lo = mid;
+    else hi = mid - 1;
+  }
+  const AdamTensor& t = a.t[lo];
+  const float* r = a.sched + c * sched_stride + 3 * lo;
+  if (r[0] == 0.f) return;
+  const float step_size = r[1], bc2_sqrt = r[2];
+  const long slot = c * slot_len, base = (long)(bx - g.bx0[lo]) * kAdamChunk;
+#pragma unroll
+  for (int k = 0; k < kAdamChunk / 256; ++k) {
+    const long i = base + k * 256 + threadIdx.x;
+    if (i < t.n) adamw_elem_slot(a, slot, t.off + i, step_size, bc2_sqrt);
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -60,6 +88,21 @@ hipError_t launch_adamw(const AdamArgs& a, hipStream_t st) {
   g.bx0[a.ntensors] = nb;
   if (nb == 0) return hipSuccess;
   adamw_kernel<<<nb, 256, 0, st>>>(a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_adamw_cells(const AdamArgs& a, int n_cells, long slot_len, const int* active,
+                              long sched_cell_stride, hipStream_t st) {
+  if (!a.sched || n_cells > 65535) return hipErrorInvalidValue;  // table-driven only; cells on grid y
+  AdamGrid g{};
+  int nb = 0;
+  for (int i = 0; i < a.ntensors; ++i) {
+    g.bx0[i] = nb;
+    nb += (int)((a.t[i].n + kAdamChunk - 1) / kAdamChunk);
+  }
+  g.bx0[a.ntensors] = nb;
+  if (nb == 0 || n_cells <= 0) return hipSuccess;
+  adamw_cells_kernel<<<dim3(nb, n_cells), 256, 0, st>>>(a, g, active, slot_len, sched_cell_stride);
   return hipGetLastError();
 }
 

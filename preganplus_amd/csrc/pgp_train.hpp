@@ -107,6 +107,12 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ P, float* __res
 __device__ __forceinline__ void adamw_elem(const AdamArgs& a, long o, float step_size, float bc2_sqrt) {
   adamw_update(a.param, a.m, a.v, o, a.grad[o], a.lr_wd, a.b1, a.b2, a.eps, step_size, bc2_sqrt);
 }
+// adamw_elem on the slot that starts `slot` floats into a's four buffers (the cell-indexed kernel)
+__device__ __forceinline__ void adamw_elem_slot(const AdamArgs& a, long slot, long o, float step_size,
+                                                float bc2_sqrt) {
+  adamw_update(a.param + slot, a.m + slot, a.v + slot, o, a.grad[slot + o], a.lr_wd, a.b1, a.b2, a.eps, step_size,
+               bc2_sqrt);
+}
 __device__ __forceinline__ void adamw_fused(const AdamFuse& f, const float* g_at, float g) {
   if (f.P) adamw_update(f.P, f.m, f.v, g_at - f.G, g, f.lr_wd, f.b1, f.b2, f.eps, f.step_size, f.bc2_sqrt);
 }

@@ -121,5 +121,21 @@ hipError_t launch_fwd_many(int H, int n, const float* win, const float* P, doubl
 hipError_t launch_infer1(int H, int K, const float* win, const float* sched, const float* P, const double* protos,
                          float* logits, float* protos_out, int* cls, int* any_anom, float* probs, int* keep,
                          int* final_t, int* gen_t, hipStream_t st);
+// The same three for a fleet of cells, one launch each (pgp_tune1_cells.hip): cell b
+// works on slot b of every per-cell array (P / G [cells][master len], state
+// [cells][2K+3], win / y / cls / loss [cells][n_steps][...], rng [cells][2]);
+// active [cells] (NULL: every cell) switches cells off, which then touch
+// nothing.  thr == 0 launches the step without dropout.  The forward's grid is
+// (n, cells): at most kMaxFwdCells cells.
+constexpr int kMaxFwdCells = 65535;
+hipError_t launch_tune1_cells(int H, int K, int n_cells, int n_steps, int step, const int* active, const float* win,
+                              const int* y, const int* cls, const float* P, float* G, double* state,
+                              double update_min, double decay, float* logits, float* protos, double* loss,
+                              unsigned int thr, float ks, const unsigned long long* rng, hipStream_t st);
+hipError_t launch_fwd_cells(int H, int n_cells, int n, const int* active, const float* win, const float* P,
+                            double* logits, double* protos, hipStream_t st);
+hipError_t launch_infer1_cells(int H, int K, int n_cells, const int* active, const float* win, const float* sched,
+                               const float* P, const double* state, float* logits, float* protos_out, int* cls,
+                               int* any_anom, float* probs, int* keep, int* final_t, int* gen_t, hipStream_t st);
 
 }  // namespace pgp

@@ -28,6 +28,8 @@
 // channel) order, models.py:399).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pgp_device.hpp"
 #include "pgp_gemm.hpp"
 #include "pgp_philox.hpp"
@@ -449,7 +451,24 @@ PGP_DEV void t1_forward(float* sm, const float* __restrict__ P, const float* __r
 // DROP (pgp_tune_step1_dropout, p > 0): train-mode dropout at the reference's
 // five sites; the masks of optimizer step rng[1] + step under seed rng[0]
 // (device memory: the step replays from a captured graph), thr / ks as T1Drop.
-template <int H, bool DROP>
+//
+// CELLS (pgp_tune_step1_many): the cell-indexed form.  Workgroup b is cell b and
+// runs step `step` of its own n_steps windows on slot b of every per-cell array
+// (P / Gd [cells][TGeo<H>::ALL], state [cells][2K+3], win [cells][n_steps][9H],
+// yv / cv [cells][n_steps][H], loss [cells][n_steps][2], logits / protos
+// [cells][2H], rng [cells][2]; offsets in 64 bits): the pointers move to the
+// slot and the step below is the single-cell one.  The slots are disjoint and no
+// workgroup waits for another; one workgroup per CU (the LDS), more cells than
+// CUs queue.  A cell whose `active` entry is 0 leaves before it touches its
+// slot.  The single-cell form's last argument is the plain step (its arguments
+// are the ones it always had).
+struct T1CellStep {
+  int step, n_steps;
+  const int* active;
+};
+template <bool CELLS>
+using T1Step = std::conditional_t<CELLS, T1CellStep, int>;
+template <int H, bool DROP, bool CELLS = false>
 __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* __restrict__ win,
                                                            const int* __restrict__ yv, const int* __restrict__ cv,
                                                            const float* __restrict__ P, float* __restrict__ Gd,
@@ -457,12 +476,32 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
                                                            double decay, float* __restrict__ logits_out,
                                                            float* __restrict__ protos_out, double* __restrict__ loss,
                                                            unsigned int thr, float ks,
-                                                           const unsigned long long* __restrict__ rng, int step) {
+                                                           const unsigned long long* __restrict__ rng,
+                                                           T1Step<CELLS> step_arg) {
   using S = T1<H>;
   using G = TGeo<H>;
   using DG = DropGeo<H>;
   constexpr int D = S::D, T = S::T, HD = S::HD, FF = S::FF, Q3 = S::Q3, NO = S::NO, L = S::L;
   constexpr int DS = S::DS, QS = S::QS, FS = S::FS;
+  int step;
+  if constexpr (CELLS) {
+    step = step_arg.step;
+    const long b = blockIdx.x;
+    if (step_arg.active && !step_arg.active[b]) return;  // uniform over the workgroup, before any barrier
+    const long ws = b * step_arg.n_steps + step;         // the cell's window of this step
+    win += ws * 9 * H;
+    yv += ws * H;
+    cv += ws * H;
+    P += b * G::ALL;
+    Gd += b * G::ALL;
+    state += b * (2 * K + 3);
+    logits_out += b * 2 * H;
+    protos_out += b * 2 * H;
+    loss += ws * 2;
+    if constexpr (DROP) rng += 2 * b;
+  } else {
+    step = step_arg;
+  }
   __shared__ __attribute__((aligned(16))) float sm[DROP ? S::TOTAL_DROP : S::TOTAL];
   [[maybe_unused]] const unsigned char* keep = reinterpret_cast<const unsigned char*>(sm + S::S_MK);
   const int tid = threadIdx.x;
@@ -737,7 +776,11 @@ __global__ __launch_bounds__(kT1Threads) void tune1_kernel(int K, const float* _
 // slope 1 = identity), ns = s + 4 tanh(W2 hg + b2); hd = Wd1 [s; ns] + bd1,
 // probs = softmax(Wd2 hd + bd2).
 // ---------------------------------------------------------------------------
-template <int H>
+// CELLS (pgp_forward1_many): workgroup b is cell b, with slot b of win
+// [cells][9H], sched [cells][H^2], P [cells][TGeo<H>::ALL] (its own transformer,
+// gen and disc sections), of every output, and the prototypes at the head of its
+// state slot (protos_dev: [cells][2K+3]); an inactive cell leaves at once.
+template <int H, bool CELLS = false>
 __global__ __launch_bounds__(kT1Threads) void infer1_kernel(int K, const float* __restrict__ win,
                                                             const float* __restrict__ sched,
                                                             const float* __restrict__ P,
@@ -745,10 +788,27 @@ __global__ __launch_bounds__(kT1Threads) void infer1_kernel(int K, const float* 
                                                             float* __restrict__ logits, float* __restrict__ protos,
                                                             int* __restrict__ cls, int* __restrict__ any_anom,
                                                             float* __restrict__ probs, int* __restrict__ keep,
-                                                            int* __restrict__ final_t, int* __restrict__ gen_t) {
+                                                            int* __restrict__ final_t, int* __restrict__ gen_t,
+                                                            const int* __restrict__ active) {
   using S = T1<H>;
   using G = TGeo<H>;
   constexpr int H2 = H * H, GIN = G::GIN, DIN = G::DIN;
+  if constexpr (CELLS) {
+    const long b = blockIdx.x;
+    if (active && !active[b]) return;
+    win += b * 9 * H;
+    sched += b * H2;
+    P += b * G::ALL;
+    protos_dev += b * (2 * K + 3);
+    logits += b * 2 * H;
+    protos += b * 2 * H;
+    cls += b * H;
+    any_anom += b;
+    probs += b * 2;
+    keep += b;
+    final_t += b * H;
+    gen_t += b * H;
+  }
   __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
   const int tid = threadIdx.x, lane = tid & 63;
   int mk_ = 0;
@@ -872,6 +932,31 @@ __global__ __launch_bounds__(kT1Threads) void fwd_many_kernel(const float* __res
   t1_forward<H>(sm, P, win + b * 9 * H, nullptr, nullptr, mk_, logits + b * 2 * H, protos + b * 2 * H);
 }
 
+// The cell-indexed form (pgp_tune_forward_cells): grid (n windows, cells);
+// window blockIdx.x of cell blockIdx.y from that cell's slot of P
+// [cells][TGeo<H>::ALL]; win [cells][n][9H], logits / protos [cells][n][2H] fp64
+template <int H>
+__global__ __launch_bounds__(kT1Threads) void fwd_cells_kernel(const int* __restrict__ active,
+                                                               const float* __restrict__ win,
+                                                               const float* __restrict__ P,
+                                                               double* __restrict__ logits,
+                                                               double* __restrict__ protos) {
+  using S = T1<H>;
+  __shared__ __attribute__((aligned(16))) float sm[S::TOTAL];
+  const long c = blockIdx.y;
+  if (active && !active[c]) return;
+  const long b = c * gridDim.x + blockIdx.x;
+  int mk_ = 0;
+  t1_forward<H>(sm, P + c * TGeo<H>::ALL, win + b * 9 * H, nullptr, nullptr, mk_, logits + b * 2 * H,
+                protos + b * 2 * H);
+}
+
+// The launches.  The cell-indexed forms are instantiated in a translation unit
+// of their own (pgp_tune1_cells.hip includes this file with PGP_T1_CELLS_TU):
+// instantiated beside the single-cell kernels they changed those kernels'
+// register allocation and schedule (the inliner sees other call counts), and the
+// single-cell entries keep the instruction streams they had.
+#ifndef PGP_T1_CELLS_TU
 #ifdef PGP_T1_PROF
 extern "C" int pgp_tune1_prof_read(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_prof), sizeof(g_t1_prof)) == hipSuccess ? 0 : -1;
@@ -886,11 +971,11 @@ hipError_t launch_infer1(int H, int K, const float* win, const float* sched, con
   switch (H) {
     case 8:
       infer1_kernel<8><<<1, kT1Threads, 0, st>>>(K, win, sched, P, protos, logits, protos_out, cls, any_anom, probs,
-                                                 keep, final_t, gen_t);
+                                                 keep, final_t, gen_t, nullptr);
       break;
     case 16:
       infer1_kernel<16><<<1, kT1Threads, 0, st>>>(K, win, sched, P, protos, logits, protos_out, cls, any_anom, probs,
-                                                  keep, final_t, gen_t);
+                                                  keep, final_t, gen_t, nullptr);
       break;
     default:
       return hipErrorInvalidValue;
@@ -952,6 +1037,74 @@ hipError_t launch_tune1_dropout(int H, int K, const float* win, const int* y, co
   return hipGetLastError();
 }
 
+#else  // PGP_T1_CELLS_TU
+// ---- the cell-indexed launches (one workgroup per cell; per-cell arrays in contiguous slots) ----
+// thr == 0: the step without dropout (rng unread)
+hipError_t launch_tune1_cells(int H, int K, int n_cells, int n_steps, int step, const int* active, const float* win,
+                              const int* y, const int* cls, const float* P, float* G, double* state,
+                              double update_min, double decay, float* logits, float* protos, double* loss,
+                              unsigned int thr, float ks, const unsigned long long* rng, hipStream_t st) {
+  if (n_cells <= 0) return hipSuccess;
+#define PGP_T1_CELLS(h, drop)                                                                                  \
+  tune1_kernel<h, drop, true><<<n_cells, kT1Threads, 0, st>>>(K, win, y, cls, P, G, state, update_min, decay,  \
+                                                              logits, protos, loss, thr, ks, rng,             \
+                                                              T1CellStep{step, n_steps, active})
+  switch (H) {
+    case 8:
+      if (thr) PGP_T1_CELLS(8, true);
+      else PGP_T1_CELLS(8, false);
+      break;
+    case 16:
+      if (thr) PGP_T1_CELLS(16, true);
+      else PGP_T1_CELLS(16, false);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef PGP_T1_CELLS
+  return hipGetLastError();
+}
+
+hipError_t launch_fwd_cells(int H, int n_cells, int n, const int* active, const float* win, const float* P,
+                            double* logits, double* protos, hipStream_t st) {
+  if (n_cells <= 0 || n <= 0) return hipSuccess;
+  if (n_cells > 65535) return hipErrorInvalidValue;  // cells on grid y (kMaxFwdCells, pgp_tune.hpp)
+  const dim3 grid(n, n_cells);
+  switch (H) {
+    case 8:
+      fwd_cells_kernel<8><<<grid, kT1Threads, 0, st>>>(active, win, P, logits, protos);
+      break;
+    case 16:
+      fwd_cells_kernel<16><<<grid, kT1Threads, 0, st>>>(active, win, P, logits, protos);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_infer1_cells(int H, int K, int n_cells, const int* active, const float* win, const float* sched,
+                               const float* P, const double* state, float* logits, float* protos_out, int* cls,
+                               int* any_anom, float* probs, int* keep, int* final_t, int* gen_t, hipStream_t st) {
+  if (n_cells <= 0) return hipSuccess;
+  switch (H) {
+    case 8:
+      infer1_kernel<8, true><<<n_cells, kT1Threads, 0, st>>>(K, win, sched, P, state, logits, protos_out, cls,
+                                                             any_anom, probs, keep, final_t, gen_t, active);
+      break;
+    case 16:
+      infer1_kernel<16, true><<<n_cells, kT1Threads, 0, st>>>(K, win, sched, P, state, logits, protos_out, cls,
+                                                              any_anom, probs, keep, final_t, gen_t, active);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+#endif  // PGP_T1_CELLS_TU
+
+#ifndef PGP_T1_CELLS_TU
 // the test tap: one step's keep bytes [DropGeo<H>::TOTAL] from the device function the step kernel fills its LDS with
 template <int H>
 __global__ __launch_bounds__(kT1Threads) void drop_masks_kernel(unsigned int thr,
@@ -978,5 +1131,6 @@ hipError_t launch_drop_masks(int H, unsigned int thr, const unsigned long long* 
   }
   return hipGetLastError();
 }
+#endif  // PGP_T1_CELLS_TU
 
 }  // namespace pgp

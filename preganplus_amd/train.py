@@ -1719,3 +1719,399 @@ class OnlineTrainStep:
             self.graph.replay()
         else:
             self.issue()
+
+
+# ---------------------------------------------------------------------------
+# A fleet of cells, each tuned on its own weights (PreGANPlus.py:51-58: every
+# PreGANPlusRecovery owns its Transformer_16; train.py:42-57, 94-109)
+# ---------------------------------------------------------------------------
+COND_TENSORS = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")   # no gradient without a positive label
+
+
+def bind_fleet(L):
+    """argtypes of the cell-indexed entries (``pgp_tune_step1_many``,
+    ``pgp_adamw_table_many``, ``pgp_tune_forward_cells``, ``pgp_forward1_many``)."""
+    if getattr(L, "_pgp_fleet_bound", False):
+        return L
+    vp, i32, dbl, f32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_longlong
+    L.pgp_tune_step1_many.argtypes = [i32] * 5 + [vp] * 7 + [dbl, dbl] + [vp] * 3 + [f32, vp] + [vp]
+    L.pgp_adamw_table_many.argtypes = ([i32, i64, vp] + [vp] * 4 + [f32] * 5 + [ctypes.POINTER(_AdamTensor), i32, vp, i64]
+                                       + [vp])
+    L.pgp_tune_forward_cells.argtypes = [i32] * 3 + [vp] * 5 + [vp]
+    L.pgp_forward1_many.argtypes = [i32] * 3 + [vp] * 13 + [vp]
+    for f in ("pgp_tune_step1_many", "pgp_adamw_table_many", "pgp_tune_forward_cells", "pgp_forward1_many"):
+        getattr(L, f).restype = i32
+    L.pgp_master_len.argtypes = [i32]
+    L.pgp_master_len.restype = ctypes.c_size_t
+    L._pgp_fleet_bound = True
+    return L
+
+
+def master_tensors(H: int) -> list:
+    """The tensor records of a master buffer in blob order, as ``Trainer.tensors``
+    holds them (section, name, offset, n, trainable), without a device."""
+    out, off = [], 0
+    for sec, name, shp in W.blob_layout(H)[:-1]:
+        cnt = int(np.prod(shp))
+        out.append({"section": sec, "name": name, "offset": off, "n": cnt, "trainable": name != "pos_encoder.pe"})
+        off += cnt
+    return out
+
+
+class FleetSchedule:
+    """The host bookkeeping of a fleet's AdamW: per cell and per tensor the
+    step counts ``Trainer.tensors[i]["step"]`` holds, advanced per ``tune()``
+    call by ``Trainer.adam_schedule_np``'s rule, for all cells at once.  No
+    device."""
+
+    def __init__(self, H: int, n_cells: int, lr: float | None = None, betas=(0.9, 0.999)):
+        self.H, self.M = int(H), int(n_cells)
+        self.tensors = master_tensors(self.H)
+        self.lr = default_lrs(self.H)["transformer"] if lr is None else lr
+        self.b1, self.b2 = betas
+        self.sel = [i for i, t in enumerate(self.tensors) if t["section"] == "transformer" and t["trainable"]]
+        self.cond = np.array([self.tensors[i]["name"] in COND_TENSORS for i in self.sel])
+        self.base_col = next(i for i, t in enumerate(self.tensors)
+                             if t["section"] == "transformer" and t["name"] == "time_encoder.weight")
+        self.steps = np.zeros((self.M, len(self.tensors)), dtype=np.float64)
+
+    def drop_bases(self) -> np.ndarray:
+        """Per cell ``Trainer.dropout_base()``: the optimizer step the next call's first step is."""
+        return self.steps[:, self.base_col].astype(np.int64)
+
+    def tables(self, positive, active=None) -> np.ndarray:
+        """positive [M,n] (window s of cell m has a positive label), active [M]
+        -> the AdamW tables [M,n,T,3] fp32 of (active, step_size, bc2_sqrt) over
+        the transformer's trainable tensors; advances the active cells' counts
+        as those n steps do.  An inactive cell's rows are zero, its counts stay."""
+        positive = np.asarray(positive, dtype=bool)
+        M, n = positive.shape
+        if M != self.M:
+            raise ValueError(f"positive: {M} cells, the fleet has {self.M}")
+        act = np.ones(M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(M)
+        on = np.where(self.cond[None, None, :], positive[:, :, None], True) & act[:, None, None]   # [M,n,T]
+        steps = self.steps[:, self.sel][:, None, :] + np.cumsum(on, axis=1)
+        st = np.maximum(steps, 1.0)
+        tab = np.empty(on.shape + (3,), dtype=np.float32)
+        tab[..., 0] = on
+        tab[..., 1] = self.lr / (1 - self.b1 ** st)
+        tab[..., 2] = np.sqrt(1 - self.b2 ** st)
+        tab[~act] = 0.0
+        if n:
+            self.steps[:, self.sel] = steps[:, -1, :]
+        return tab
+
+
+def fleet_staging_layout(H: int, n_cells: int, n: int, K: int, n_tensors: int):
+    """The input staging of one ``FleetTuner.tune`` call, uploaded with one
+    copy: [(name, numpy dtype, shape, byte offset, bytes)], total bytes.  Every
+    part starts 8-byte aligned (state is fp64, rng 64-bit words)."""
+    M = n_cells
+    parts = [("W", np.float32, (M, n, 3, 3 * H)), ("Y", np.int32, (M, n, H)), ("C", np.int32, (M, n, H)),
+             ("sched", np.float32, (M, n, n_tensors, 3)), ("active", np.int32, (M,)),
+             ("state", np.float64, (M, 2 * K + 3)), ("rng", np.int64, (M, 2))]
+    off, lay = 0, []
+    for name, dt, shp in parts:
+        nb = int(np.prod(shp)) * np.dtype(dt).itemsize
+        off = (off + 7) // 8 * 8
+        lay.append((name, dt, shp, off, nb))
+        off += nb
+    return lay, (off + 7) // 8 * 8
+
+
+_NP2TORCH = {np.float32: torch.float32, np.int32: torch.int32, np.float64: torch.float64, np.int64: torch.int64}
+
+
+class _FleetGraph:
+    """One ``FleetTuner.tune`` call captured as a HIP graph: per step one
+    ``pgp_tune_step1_many`` and one ``pgp_adamw_table_many`` launch for all
+    cells, then (``score``) one ``pgp_tune_forward_cells`` — 2n + 1 launches
+    whatever the fleet's size — and the copy of the state into the output
+    gather.  Inputs in one staging buffer (``fleet_staging_layout``), outputs
+    in one fp64 buffer: loss [M,n,2] | state [M,2K+3] | logits [M,n,H,2] |
+    protos [M,n,H,2]."""
+
+    def __init__(self, ft: "FleetTuner", n: int, score: bool):
+        H, M, K, dev = ft.H, ft.M, ft.K, ft.device
+        self.n, self.score = n, score
+        lay, total = fleet_staging_layout(H, M, n, K, len(ft.sel))
+        self.din = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self.hviews = {}
+        for name, dt, shp, o, nb in lay:
+            setattr(self, name, self.din[o:o + nb].view(_NP2TORCH[dt]).view(shp))
+            self.hviews[name] = self.hin[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
+        S = 2 * K + 3
+        self.o_state = 2 * n * M
+        self.o_lg = self.o_state + M * S
+        self.o_pr = self.o_lg + 2 * n * H * M
+        nout = self.o_lg + (4 * n * H * M if score else 0)
+        self.dout = torch.zeros(nout, dtype=torch.float64, device=dev)
+        self.hout = torch.zeros(nout, dtype=torch.float64).pin_memory()
+        self.loss = self.dout[:self.o_state]
+        self.graph = None
+
+    def issue(self, ft: "FleetTuner"):
+        """The call's launches on the current stream, in the graph's order."""
+        for i in range(self.n):
+            ft.step_many(self, i)
+            ft.adamw_many(self, i)
+        self.dout[self.o_state:self.o_lg].copy_(self.state.view(-1))
+        if self.score:
+            ft.forward_cells(self)
+
+    def capture(self, ft: "FleetTuner"):
+        self.graph = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize(ft.device)
+        with torch.cuda.graph(self.graph):
+            self.issue(ft)
+
+
+class FleetTuner:
+    """M decision models of one host count in contiguous device slots, tuned
+    together: what M ``Trainer`` + ``TuneState`` pairs running ``backprop``
+    one after another compute, bit for bit per cell, in one graph of 2n + 1
+    launches (``pgp_tune_step1_many`` / ``pgp_adamw_table_many`` /
+    ``pgp_tune_forward_cells``), and the per-interval forward of every cell in
+    one launch (``pgp_forward1_many``).  8 or 16 hosts (``FUSED_STEP_HOSTS``).
+
+    weights: M weight dicts (``weights.synth_weights``' form; every cell the
+    same number of prototypes); extras: per cell ``Trainer``'s ``extra``
+    (optimizer state) or None; dropout / dropout_seeds: ``Trainer``'s
+    ``dropout`` for every cell and ``dropout_seed`` per cell.
+
+    Per cell it holds ``states[m]`` (a ``TuneState``), the per-tensor AdamW
+    step counts (``sched.steps[m]``) and the dropout seed, with the meaning
+    they have in ``Trainer``."""
+
+    def __init__(self, hosts: int, weights, extras=None, dropout: float = 0.0, dropout_seeds=None, device=None,
+                 lrs: dict | None = None, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8):
+        self.H = int(hosts)
+        if self.H not in FUSED_STEP_HOSTS:
+            raise ValueError(f"FleetTuner runs the fused batch-1 step: n_hosts in {FUSED_STEP_HOSTS}, not {self.H}")
+        self.dropout = float(dropout)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"dropout {dropout} outside [0, 1)")
+        weights = list(weights)
+        self.M = M = len(weights)
+        if M == 0:
+            raise ValueError("a fleet needs at least one cell")
+        if extras is not None and len(extras) != M:
+            raise ValueError(f"extras: {len(extras)} entries for {M} cells")
+        seeds = [0] * M if dropout_seeds is None else [int(s) & (2 ** 64 - 1) for s in dropout_seeds]
+        if len(seeds) != M:
+            raise ValueError(f"dropout_seeds: {len(seeds)} entries for {M} cells")
+        self.seeds = seeds
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._L = L = bind_fleet(_native.lib())
+        self.lrs = dict(default_lrs(self.H), **(lrs or {}))
+        self.wd, self.b1, self.b2, self.eps = weight_decay, betas[0], betas[1], eps
+        self.sched = FleetSchedule(self.H, M, self.lrs["transformer"], betas)
+        self.tensors = self.sched.tensors
+        self.sel = [self.tensors[i] for i in self.sched.sel]
+        self.slot_len = n = int(L.pgp_master_len(self.H))
+        if n == 0 or n != self.tensors[-1]["offset"] + self.tensors[-1]["n"]:
+            raise ValueError(f"H={hosts}: master layout mismatch")
+        Ks = {np.asarray(w["prototypes"]).shape[0] for w in weights}
+        if len(Ks) != 1:
+            raise ValueError(f"every cell needs the same number of prototypes, got {sorted(Ks)}")
+        self.K = Ks.pop()
+        self._template = weights[0]
+        P = np.stack([W.pack_blob(w, self.H)[:n].astype(np.float32) for w in weights])
+        m, v = np.zeros_like(P), np.zeros_like(P)
+        for c, extra in enumerate(extras or []):
+            for i, t in enumerate(self.tensors):
+                key = f"opt/{t['section']}/{t['name']}"
+                if extra and f"{key}/exp_avg" in extra:
+                    m[c, t["offset"]:t["offset"] + t["n"]] = np.asarray(extra[f"{key}/exp_avg"]).reshape(-1)
+                    v[c, t["offset"]:t["offset"] + t["n"]] = np.asarray(extra[f"{key}/exp_avg_sq"]).reshape(-1)
+                    self.sched.steps[c, i] = float(extra[f"{key}/step"])
+        dev = self.device
+        self.P = torch.from_numpy(P).to(dev)
+        self.G = torch.zeros_like(self.P)
+        self.m = torch.from_numpy(m).to(dev)
+        self.v = torch.from_numpy(v).to(dev)
+        self.states = [TuneState(w["prototypes"]) for w in weights]
+        self.state0 = torch.tensor(np.stack([s.vector() for s in self.states]), dtype=torch.float64, device=dev)
+        self.state_dev = self.state0           # the device tensor [M,2K+3] that holds the fleet's current state
+        self.logits = torch.zeros((M, self.H, 2), dtype=torch.float32, device=dev)
+        self.protos = torch.zeros((M, self.H, 2), dtype=torch.float32, device=dev)
+        self._desc = (_AdamTensor * len(self.sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in self.sel])
+        self._graphs = {}
+        self._detect_io = None
+
+    def _stream(self):
+        idx = self.device.index
+        if idx is not None and _RAW_STREAM is not None:
+            return ctypes.c_void_p(_RAW_STREAM(idx))
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ---------------- the three launches, on a graph's buffers ----------------
+    def step_many(self, g: _FleetGraph, i: int):
+        """Step i of every active cell (``pgp_tune_step1_many``)."""
+        _native.check(self._L.pgp_tune_step1_many(
+            self.H, self.K, self.M, g.n, i, g.active.data_ptr(), g.W.data_ptr(), g.Y.data_ptr(), g.C.data_ptr(),
+            self.P.data_ptr(), self.G.data_ptr(), g.state.data_ptr(), PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY,
+            self.logits.data_ptr(), self.protos.data_ptr(), g.loss.data_ptr(), self.dropout, g.rng.data_ptr(),
+            self._stream()), "pgp_tune_step1_many")
+
+    def adamw_many(self, g: _FleetGraph, i: int):
+        """Step i's AdamW of every active cell from its own table row (``pgp_adamw_table_many``)."""
+        T = len(self.sel)
+        _native.check(self._L.pgp_adamw_table_many(
+            self.M, self.slot_len, g.active.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), self.m.data_ptr(),
+            self.v.data_ptr(), self.lrs["transformer"], self.wd, self.b1, self.b2, self.eps, self._desc, T,
+            g.sched.data_ptr() + 4 * 3 * T * i, g.n * T * 3, self._stream()), "pgp_adamw_table_many")
+
+    def forward_cells(self, g: _FleetGraph):
+        """accuracy()'s forward of every active cell on its own windows (``pgp_tune_forward_cells``)."""
+        _native.check(self._L.pgp_tune_forward_cells(
+            self.H, self.M, g.n, g.active.data_ptr(), g.W.data_ptr(), self.P.data_ptr(),
+            g.dout[g.o_lg:].data_ptr(), g.dout[g.o_pr:].data_ptr(), self._stream()), "pgp_tune_forward_cells")
+
+    def graph(self, n: int, score: bool = True, capture: bool = True) -> _FleetGraph:
+        """The call's buffers and captured graph, cached per (n, score); the
+        fleet's size, prototype count and dropout are fixed per tuner."""
+        key = (self.M, int(n), self.K, bool(score), self.dropout)
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = _FleetGraph(self, int(n), bool(score))
+        if capture and g.graph is None:
+            g.capture(self)
+        return g
+
+    def stage(self, g: _FleetGraph, wins, anom, cls, active=None):
+        """Fill the graph's pinned staging from the call's inputs and the
+        host bookkeeping (resetting num_zero / num_ones, taking each cell's
+        dropout base before its counts advance, building its AdamW table).
+        Returns the checked (anom, cls, active)."""
+        M, n, H = self.M, g.n, self.H
+        wins = np.asarray(wins, dtype=np.float32).reshape(M, n, 3, 3 * H)
+        anom = np.asarray(anom).reshape(M, n, H)
+        cls = np.asarray(cls).reshape(M, n, H)
+        act = np.ones(M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(M)
+        bad = (anom > 0) & ((cls < 0) | (cls > 2)) & act[:, None, None]
+        if bad.any():
+            raise ValueError("anomalous host with a class outside 0..2 (triplet_loss, train.py:15-17)")
+        for c in np.flatnonzero(act):
+            self.states[c].num_zero, self.states[c].num_ones = 1, 1
+        bases = self.sched.drop_bases()
+        tab = self.sched.tables(np.any(anom > 0, axis=2), act)
+        hv = g.hviews
+        hv["W"][...] = wins
+        hv["Y"][...] = anom
+        hv["C"][...] = cls
+        hv["sched"][...] = tab
+        hv["active"][...] = act
+        hv["state"][...] = np.stack([s.vector() for s in self.states])
+        hv["rng"][...] = np.array([[s, int(b) & (2 ** 64 - 1)] for s, b in zip(self.seeds, bases)],
+                                  dtype=np.uint64).view(np.int64)
+        return anom, cls, act
+
+    def results(self, g: _FleetGraph, out, anom, cls, act):
+        """Per cell what ``backprop`` returns from the downloaded gather; updates the active cells' host state."""
+        M, n, H, S = self.M, g.n, self.H, 2 * self.K + 3
+        self.state_dev = g.state
+        loss = out[:g.o_state].reshape(M, n, 2)
+        state = out[g.o_state:g.o_lg].reshape(M, S)
+        res = [None] * M
+        for c in np.flatnonzero(act):
+            self.states[c].from_vector(state[c])
+            losses = [tuple(r) for r in loss[c].tolist()]
+            if not g.score:
+                res[c] = losses
+                continue
+            lg = out[g.o_lg:g.o_pr].reshape(M, n, H, 2)[c]
+            pr = out[g.o_pr:].reshape(M, n, H, 2)[c]
+            try:
+                scores = accuracy_scores(lg, pr, anom[c], cls[c], self.states[c].protos)
+            except ZeroDivisionError:   # no window of the cell has a positive label: the lone call raises here
+                scores = None           # (train.py:109); one such cell must not stop the fleet
+            res[c] = (losses, scores)
+        return res
+
+    def tune(self, wins, anom, cls, active=None, score: bool = True):
+        """One interval's tuning of every active cell: wins [M,n,3,3H], anom /
+        cls [M,n,H], active [M] (None: all).  Returns a list of M entries: for
+        an active cell what ``backprop(tr_m, st_m, wins[m], anom[m], cls[m],
+        score=score)`` returns (with ``score``, the scores are None where that
+        call raises ZeroDivisionError: a cell without a positive label in any
+        window), None for the others, whose slots and counts stay untouched.
+        One upload from pinned staging (``active`` among the inputs: one graph
+        serves any subset), one graph replay, one download."""
+        n = np.asarray(wins).shape[1]
+        if n == 0:
+            return [(([], None) if score else []) for _ in range(self.M)]
+        g = self.graph(n, score)
+        anom, cls, act = self.stage(g, wins, anom, cls, active)
+        g.din.copy_(g.hin, non_blocking=True)
+        g.graph.replay()
+        g.hout.copy_(g.dout, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.results(g, g.hout.numpy(), anom, cls, act)
+
+    # ---------------- the per-interval forward ----------------
+    def detect(self, windows, scheds, active=None) -> dict:
+        """run_model's forward of every cell on its own weights and prototypes
+        (``pgp_forward1_many``): windows [M,3,3H], scheds [M,H,H] ->
+        ``DecisionModel``'s output dict with batch M (device tensors).  An
+        inactive cell's rows are left as they were."""
+        M, H, dev = self.M, self.H, self.device
+        if self._detect_io is None:
+            f32, i32 = torch.float32, torch.int32
+            spec = [("logits", f32, (M, H, 2)), ("protos", f32, (M, H, 2)), ("cls", i32, (M, H)), ("any", i32, (M,)),
+                    ("probs", f32, (M, 2)), ("keep", i32, (M,)), ("final_target", i32, (M, H)),
+                    ("gen_target", i32, (M, H))]
+            out = {name: torch.zeros(shp, dtype=dt, device=dev) for name, dt, shp in spec}
+            out["latent"] = None
+            self._detect_io = (out, torch.ones(M, dtype=torch.int32, device=dev))
+        out, act = self._detect_io
+        to = lambda a, shp: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float32))).to(
+            dev, torch.float32).reshape(shp).contiguous()
+        w, s = to(windows, (M, 3, 3 * H)), to(scheds, (M, H, H))
+        act.copy_(torch.as_tensor(np.ones(M, dtype=np.int32) if active is None
+                                  else np.asarray(active, dtype=bool).reshape(M).astype(np.int32)))
+        p = lambda k: out[k].data_ptr()
+        _native.check(self._L.pgp_forward1_many(
+            H, self.K, M, act.data_ptr(), w.data_ptr(), s.data_ptr(), self.P.data_ptr(), self.state_dev.data_ptr(),
+            p("logits"), p("protos"), p("cls"), p("any"), p("probs"), p("keep"), p("final_target"), p("gen_target"),
+            self._stream()), "pgp_forward1_many")
+        return out
+
+    # ---------------- one cell as a lone Trainer, and back ----------------
+    def trainer(self, m: int):
+        """Slot m as a lone ``Trainer`` + ``TuneState`` (weights, moments,
+        step counts, dropout seed, prototypes, factor): checkpoints and the
+        per-cell GAN step run through the single-cell code on it."""
+        tr = Trainer(self.H, self._template, lrs=self.lrs, device=self.device, max_batch=1, weight_decay=self.wd,
+                     betas=(self.b1, self.b2), eps=self.eps, dropout=self.dropout, dropout_seed=self.seeds[m])
+        tr.P.copy_(self.P[m])
+        tr.G.copy_(self.G[m])
+        tr.m.copy_(self.m[m])
+        tr.v.copy_(self.v[m])
+        for t, s in zip(tr.tensors, self.sched.steps[m]):
+            t["step"] = float(s)
+        if tr.dropout > 0:
+            tr.set_dropout_base(tr.dropout_base())
+        st = TuneState(self.states[m].protos.copy(), self.states[m].factor)
+        st.num_zero, st.num_ones = self.states[m].num_zero, self.states[m].num_ones
+        return tr, st
+
+    def load_cell(self, m: int, tr: Trainer, st: TuneState):
+        """The reverse of ``trainer(m)``: slot m continues from that trainer and state."""
+        if tr.H != self.H or st.protos.shape[0] != self.K:
+            raise ValueError("load_cell: host or prototype count differs from the fleet's")
+        if tr.dropout != self.dropout:
+            raise ValueError(f"load_cell: the trainer's dropout {tr.dropout} differs from the fleet's {self.dropout}")
+        self.P[m].copy_(tr.P)
+        self.G[m].copy_(tr.G)
+        self.m[m].copy_(tr.m)
+        self.v[m].copy_(tr.v)
+        self.sched.steps[m] = [t["step"] for t in tr.tensors]
+        self.seeds[m] = tr.dropout_seed
+        s = TuneState(st.protos.copy(), st.factor)
+        s.num_zero, s.num_ones = st.num_zero, st.num_ones
+        self.states[m] = s
+        self.state_dev[m].copy_(torch.from_numpy(s.vector()))
