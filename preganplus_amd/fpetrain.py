@@ -39,19 +39,7 @@ class FPETrainer:
                  betas=(0.9, 0.999), eps=1e-8, H=16):
         self.H = H
         self.device = torch.device(device)
-        L = _native.lib()
-        self._L = L
-        if not getattr(L, "_pgp_fpetrain_bound", False):
-            vp, i32, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-            L.pgp_fpe_param_len.argtypes = [i32]
-            L.pgp_fpe_param_len.restype = ctypes.c_size_t
-            L.pgp_fpe_train_step.argtypes = [i32, i32] + [vp] * 7 + [dbl, dbl, vp, vp]
-            L.pgp_fpe_train_step.restype = i32
-            L.pgp_fpe_forward_many.argtypes = [i32, i32] + [vp] * 5 + [vp]
-            L.pgp_fpe_forward_many.restype = i32
-            L.pgp_adamw.argtypes = [vp] * 4 + [ctypes.c_float] * 5 + [ctypes.POINTER(_AdamTensor), i32, vp]
-            L.pgp_adamw.restype = i32
-            L._pgp_fpetrain_bound = True
+        self._L = L = _native.lib()
         n = int(L.pgp_fpe_param_len(H))
         if n == 0:
             raise ValueError(f"FPE training: H={H} not supported (supported host counts: "

@@ -64,22 +64,8 @@ class GOBIOptimizer:
         if weights is None:
             weights, self.max_ips = load_weights()
         L = _native.lib()
-        vp = ctypes.c_void_p
-        L.pgp_gobi_weight_len.argtypes = [ctypes.c_int]
-        L.pgp_gobi_weight_len.restype = ctypes.c_size_t
-        L.pgp_gobi_create.argtypes = [ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
         # the fleet entries; a PGP_LIB build from before them (an A/B against an older library) serves one model
         fleet = hasattr(L, "pgp_gobi_create_many")
-        if fleet:
-            L.pgp_gobi_create_many.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-            L.pgp_gobi_model_count.argtypes = [vp]
-            L.pgp_gobi_set_model.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
-            L.pgp_gobi_optimize_groups.argtypes = [vp, ctypes.c_int, ctypes.c_int] + [vp] * 5 + [ctypes.c_int, vp, vp]
-            L.pgp_gobi_plan_groups.argtypes = [ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int]
-        L.pgp_gobi_optimize.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, vp]
-        L.pgp_gobi_destroy.argtypes = [vp]
-        L.pgp_gobi_last_error.argtypes = []
-        L.pgp_gobi_last_error.restype = ctypes.c_char_p
         self._L = L
         many = isinstance(weights, (list, tuple))
         if many and not weights:
@@ -91,6 +77,7 @@ class GOBIOptimizer:
             if blob.size != L.pgp_gobi_weight_len(H):
                 raise ValueError(f"GOBI weight blob {blob.size} != {L.pgp_gobi_weight_len(H)}")
         torch.cuda.set_device(self.device)
+        vp = ctypes.c_void_p
         h = vp()
         if many:
             blob = np.ascontiguousarray(np.stack(blobs))

@@ -29,6 +29,7 @@ import torch
 from . import _native
 from .gobi import _ORDER, H
 
+bind_many = _native.bind   # the earlier helper's name: the previous release's tests reach the library through it
 LR, WEIGHT_DECAY, BETAS, EPS = 1e-4, 1e-5, (0.9, 0.999), 1e-8   # train.py:53 (torch.optim.Adam's defaults)
 SHAPES = {"find.0.weight": (128, H * (H + 2)), "find.0.bias": (128,), "find.2.weight": (128, 128),
           "find.2.bias": (128,), "find.4.weight": (64, 128), "find.4.bias": (64,), "find.6.weight": (2, 64),
@@ -152,17 +153,7 @@ class GOBITrainer:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("GOBITrainer runs on the GPU only (no CPU fallback)")
-        L = _native.lib()
-        self._L = L
-        if not getattr(L, "_pgp_gobitrain_bound", False):
-            vp, i32, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-            L.pgp_gobi_weight_len.argtypes = [i32]
-            L.pgp_gobi_weight_len.restype = ctypes.c_size_t
-            L.pgp_gobi_train_steps.argtypes = [i32, i32, i32] + [vp] * 6 + [ctypes.c_longlong] + [dbl] * 5 + [vp, vp]
-            L.pgp_gobi_train_steps.restype = i32
-            L.pgp_gobi_train_eval.argtypes = [i32, i32, i32] + [vp] * 6
-            L.pgp_gobi_train_eval.restype = i32
-            L._pgp_gobitrain_bound = True
+        self._L = L = _native.lib()
         if weights is None:
             weights = fresh_weights(seed)
         for k in _ORDER:
@@ -417,7 +408,7 @@ class GOBIFleetTrainer:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("GOBIFleetTrainer runs on the GPU only (no CPU fallback)")
-        self._L = bind_many(_native.lib())
+        self._L = _native.lib()
         self.n_models = int(P.shape[0])
         assert P.shape[1] == self._L.pgp_gobi_weight_len(H)
         with torch.cuda.device(self.device):
@@ -533,17 +524,3 @@ class GOBIFleetTrainer:
             o, n = self._off[self.dataset_of[m]], self.n_samples(m)
             t.feats, t.targets, t.n_samples = self.feats[o:o + n].clone(), self.targets[o:o + n].clone(), n
         return t
-
-
-def bind_many(L):
-    """argtypes of the fleet entries (once per library)."""
-    if not getattr(L, "_pgp_gobifleet_bound", False):
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-        L.pgp_gobi_weight_len.argtypes = [i32]
-        L.pgp_gobi_weight_len.restype = ctypes.c_size_t
-        L.pgp_gobi_train_steps_many.argtypes = [i32, i32, vp, i64, vp, vp, i64] + [vp] * 7
-        L.pgp_gobi_train_steps_many.restype = i32
-        L.pgp_gobi_train_eval_many.argtypes = [i32, i32, vp, i64, vp, vp, i64] + [vp] * 5
-        L.pgp_gobi_train_eval_many.restype = i32
-        L._pgp_gobifleet_bound = True
-    return L

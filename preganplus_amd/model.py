@@ -55,7 +55,6 @@ class DecisionModel:
         (natural fp32 layout, preganplus_amd.train.Trainer.P)."""
         pr = np.ascontiguousarray(np.asarray(prototypes, dtype=np.float64))
         L = self._L
-        L.pgp_load_weights_master.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         torch.cuda.synchronize(self.device)
         _native.check(L.pgp_load_weights_master(self._h, ctypes.c_void_p(P.data_ptr()),
                                                 pr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
@@ -73,7 +72,6 @@ class DecisionModel:
         if protos_dev.dtype != torch.float64 or protos_dev.numel() != 2 * self.K or not protos_dev.is_contiguous():
             raise ValueError(f"protos_dev must be contiguous float64 [{self.K},2] on the device")
         L = self._L
-        L.pgp_repack_master_sections.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         _native.check(L.pgp_repack_master_sections(self._h, ctypes.c_void_p(P.data_ptr()),
                                                    ctypes.c_void_p(protos_dev.data_ptr()), int(sections),

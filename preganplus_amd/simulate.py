@@ -106,10 +106,6 @@ class Simulation:
         if self.device.type != "cuda":
             raise ValueError("Simulation runs on the GPU only (no CPU fallback)")
         L = _native.lib()
-        vp = ctypes.c_void_p
-        L.pgp_sim_env_len.argtypes = [ctypes.c_int]
-        L.pgp_sim_env_len.restype = ctypes.c_size_t
-        L.pgp_simulate.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
         self._L = L
         if L.pgp_sim_env_len(H) != env_len(H):
             raise RuntimeError("libpreganplus record layout differs from simulate.env_len")

@@ -25,6 +25,7 @@ import torch
 
 from . import _native
 from . import weights as W
+from ._native import _COLL_FN, _AdamTensor, _OnlineDesc, _OnlineTensor  # noqa: F401  (the header's structs)
 
 PROTO_UPDATE_FACTOR = 0.2   # constants.py:13
 PROTO_UPDATE_MIN = 0.02     # constants.py:14
@@ -36,11 +37,6 @@ PERCENTILES = 98            # constants.py:11
 # the current stream's raw handle by device index (torch's C++ accessor; None
 # if this torch lacks it, then Trainer._stream takes the public API)
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-class _AdamTensor(ctypes.Structure):
-    _fields_ = [("offset", ctypes.c_longlong), ("n", ctypes.c_int), ("active", ctypes.c_int),
-                ("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float)]
 
 
 def default_lrs(H):
@@ -63,8 +59,6 @@ def tune_plan_info(H: int, batch: int, fwd_batch: int | None = None) -> dict:
     the busiest dW workgroup, the forward decoder's split-K parts, the decoder
     weight gradient's window parts."""
     L = _native.lib()
-    L.pgp_tune_plan_info.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
-    L.pgp_tune_plan_info.restype = ctypes.c_int
     n = len(TUNE_PLAN_FIELDS)
     out = (ctypes.c_int * n)()
     rc = L.pgp_tune_plan_info(H, batch if fwd_batch is None else fwd_batch, batch, out, n)
@@ -79,8 +73,6 @@ def gan_plan_info(H: int, batch: int) -> int:
     """k-slices per 16-environment block of the GAN step at that batch
     (``pgp_gan_plan_info``; 1: the unsplit form)."""
     L = _native.lib()
-    L.pgp_gan_plan_info.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.pgp_gan_plan_info.restype = ctypes.c_int
     rc = L.pgp_gan_plan_info(H, batch)
     if rc < 0:
         _native.check(rc, "pgp_gan_plan_info")
@@ -108,9 +100,7 @@ class Trainer:
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        L = _native.lib()
-        self._L = L
-        self._bind()
+        self._L = L = _native.lib()
         self._desc_cache = {}
         n = L.pgp_master_len(self.H)
         if n == 0:
@@ -150,58 +140,6 @@ class Trainer:
         if self.dropout > 0:
             self.set_dropout_base(self.dropout_base())
         self._alloc(max_batch)
-
-    def _bind(self):
-        L = self._L
-        if getattr(L, "_pgp_train_bound", False):
-            return
-        vp, i32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        L.pgp_master_len.argtypes = [i32]
-        L.pgp_master_len.restype = sz
-        L.pgp_master_offset.argtypes = [i32, i32]
-        L.pgp_master_offset.restype = sz
-        L.pgp_tune_workspace_len.argtypes = [i32, i32]
-        L.pgp_tune_workspace_len.restype = sz
-        L.pgp_gan_workspace_len.argtypes = [i32, i32]
-        L.pgp_gan_workspace_len.restype = sz
-        L.pgp_tune_forward.argtypes = [i32, i32] + [vp] * 6 + [vp]
-        L.pgp_tune_backward.argtypes = [i32, i32] + [vp] * 8 + [vp]
-        L.pgp_tune_backward_prefix.argtypes = [i32, i32, i32] + [vp] * 8 + [vp]
-        L.pgp_gan_forward.argtypes = [i32, i32] + [vp] * 6 + [vp]
-        L.pgp_gan_disc_backward.argtypes = [i32, i32] + [vp] * 4 + [vp]
-        L.pgp_gan_gen_backward.argtypes = [i32, i32] + [vp] * 3 + [vp]
-        L.pgp_gan_probs.argtypes = [i32, i32, vp, vp, vp]
-        L.pgp_adamw.argtypes = [vp] * 4 + [ctypes.c_float] * 5 + [ctypes.POINTER(_AdamTensor), i32, vp]
-        L.pgp_load_weights_master.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double)]
-        L.pgp_tune_targets.argtypes = [i32, i32] + [vp] * 5 + [ctypes.c_double] * 2 + [vp] * 3 + [vp]
-        L.pgp_adamw_table.argtypes = ([vp] * 4 + [ctypes.c_float] * 5 + [ctypes.POINTER(_AdamTensor), i32, vp]
-                                      + [vp])
-        dbl = ctypes.c_double
-        L.pgp_tune_step1.argtypes = [i32, i32] + [vp] * 6 + [dbl, dbl] + [vp] * 3 + [vp]
-        L.pgp_tune_step1_dropout.argtypes = ([i32, i32] + [vp] * 6 + [dbl, dbl] + [vp] * 3
-                                             + [ctypes.c_float, vp, i32] + [vp])
-        L.pgp_tune_dropout_masks.argtypes = [i32, ctypes.c_float, vp, i32, vp] + [vp]
-        L.pgp_tune_dropout_mask_len.argtypes = [i32]
-        L.pgp_tune_dropout_mask_len.restype = sz
-        L.pgp_forward1.argtypes = [i32, i32] + [vp] * 12 + [vp]
-        L.pgp_tune_forward_many.argtypes = [i32, i32] + [vp] * 4 + [vp]
-        L.pgp_gan_forward1.argtypes = [i32] + [vp] * 6 + [vp]
-        f32 = ctypes.c_float
-        L.pgp_gan_step1.argtypes = ([i32] + [vp] * 5 + [f32] * 6 + [ctypes.POINTER(_AdamTensor), i32, vp]
-                                    + [ctypes.POINTER(_AdamTensor), i32, vp] + [vp] * 3 + [vp])
-        L.pgp_tune_dataset.argtypes = [i32, i32, i32] + [vp] * 6 + [vp]
-        L.pgp_tune_targets_dp_workspace_len.argtypes = [i32]
-        L.pgp_tune_targets_dp_workspace_len.restype = sz
-        L.pgp_tune_targets_dp.argtypes = [i32, i32, i32] + [vp] * 5 + [dbl] + [vp] * 5 + [vp]
-        L.pgp_tune_state_apply.argtypes = [i32, vp, vp, dbl, i32, ctypes.POINTER(ctypes.c_int), vp, vp,
-                                           dbl, dbl, dbl, vp]
-        for f in ("pgp_tune_forward", "pgp_tune_backward", "pgp_tune_backward_prefix", "pgp_gan_forward", "pgp_gan_disc_backward",
-                  "pgp_gan_gen_backward", "pgp_adamw", "pgp_load_weights_master", "pgp_tune_targets",
-                  "pgp_adamw_table", "pgp_tune_dataset", "pgp_tune_targets_dp", "pgp_tune_state_apply",
-                  "pgp_gan_probs", "pgp_tune_step1", "pgp_forward1", "pgp_tune_forward_many",
-                  "pgp_gan_forward1", "pgp_gan_step1", "pgp_tune_step1_dropout", "pgp_tune_dropout_masks"):
-            getattr(L, f).restype = i32
-        L._pgp_train_bound = True
 
     def _alloc(self, B):
         H, dev, L = self.H, self.device, self._L
@@ -1417,46 +1355,9 @@ def train_gan_batched(tr: Trainer, sim, envs, emb, sched, out=None, target=None,
         tr.adam_step_table("gen", tr.trainable("gen"), rows[1])
     return out, target
 
-class _OnlineTensor(ctypes.Structure):
-    _fields_ = [("offset", ctypes.c_longlong), ("n", ctypes.c_int), ("section", ctypes.c_int),
-                ("cond", ctypes.c_int), ("step", ctypes.c_double)]
 
-
-_vp, _dp = ctypes.c_void_p, ctypes.c_double
-
-
-class _OnlineDesc(ctypes.Structure):
-    """pgp_online_desc (include/preganplus.h)."""
-    _fields_ = ([(n, ctypes.c_int) for n in ("n_hosts", "n_env", "n_rows", "n_protos")]
-                + [(n, _vp) for n in ("series", "train_max", "sched", "envs", "P", "G", "exp_avg", "exp_avg_sq",
-                                      "tune_ws", "logits", "protos", "windows", "y", "cls", "state", "mult", "tgt",
-                                      "loss", "inc", "dp_ws", "adam_rows", "cond_steps", "gan_ws", "ns", "probs",
-                                      "emb", "sim_out", "target")]
-                + [("tensors", ctypes.POINTER(_OnlineTensor)), ("n_tensors", ctypes.c_int), ("n_cond", ctypes.c_int),
-                   ("lr", _dp * 3)]
-                + [(n, _dp) for n in ("weight_decay", "beta1", "beta2", "eps", "update_min", "decay")])
-
-
-_COLL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p)
 ONLINE_STAGES = ("dataset", "embedding", "train_gan", "tune_model", "forward", "targets", "backward", "exchange",
                  "apply_adamw", "main")
-
-
-def _bind_online(L):
-    if getattr(L, "_pgp_online_bound", False):
-        return
-    L.pgp_online_create.argtypes = [ctypes.POINTER(_OnlineDesc), ctypes.POINTER(ctypes.c_void_p)]
-    L.pgp_online_destroy.argtypes = [ctypes.c_void_p]
-    L.pgp_online_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _COLL_FN, ctypes.c_void_p]
-    L.pgp_online_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.pgp_online_stage_ms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.pgp_online_steps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    L.pgp_online_gan_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.pgp_online_issue_worker.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    for f in ("pgp_online_create", "pgp_online_destroy", "pgp_online_step", "pgp_online_timing",
-              "pgp_online_stage_ms", "pgp_online_steps", "pgp_online_gan_step", "pgp_online_issue_worker"):
-        getattr(L, f).restype = ctypes.c_int
-    L._pgp_online_bound = True
 
 
 def _destroy_online(L, h):
@@ -1531,7 +1432,6 @@ class OnlineTrainStep:
     # -- the native step (pgp_online_*) --
     def _create_native(self, sim):
         tr, tun, L = self.tr, self.tun, self.tr._L
-        _bind_online(L)
         H, E, R, B = tr.H, self.E, self.R, self.B
         wins, y, cls, _, allw = self.bufs
         sel = [t for t in tr.tensors if t["trainable"]]
@@ -1559,7 +1459,7 @@ class OnlineTrainStep:
         d.tensors = self._tensors
         d.n_tensors = len(sel)
         d.n_cond = len(tun.cond)
-        d.lr = (_dp * 3)(tr.lrs["transformer"], tr.lrs["gen"], tr.lrs["disc"])
+        d.lr = (ctypes.c_double * 3)(tr.lrs["transformer"], tr.lrs["gen"], tr.lrs["disc"])
         d.weight_decay, d.beta1, d.beta2, d.eps = tr.wd, tr.b1, tr.b2, tr.eps
         d.update_min, d.decay = PROTO_UPDATE_MIN, PROTO_FACTOR_DECAY
         if tr.cap < B + E or L.pgp_tune_workspace_len(H, B + E) > tr.ws.numel():
@@ -1726,25 +1626,7 @@ class OnlineTrainStep:
 # PreGANPlusRecovery owns its Transformer_16; train.py:42-57, 94-109)
 # ---------------------------------------------------------------------------
 COND_TENSORS = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")   # no gradient without a positive label
-
-
-def bind_fleet(L):
-    """argtypes of the cell-indexed entries (``pgp_tune_step1_many``,
-    ``pgp_adamw_table_many``, ``pgp_tune_forward_cells``, ``pgp_forward1_many``)."""
-    if getattr(L, "_pgp_fleet_bound", False):
-        return L
-    vp, i32, dbl, f32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_longlong
-    L.pgp_tune_step1_many.argtypes = [i32] * 5 + [vp] * 7 + [dbl, dbl] + [vp] * 3 + [f32, vp] + [vp]
-    L.pgp_adamw_table_many.argtypes = ([i32, i64, vp] + [vp] * 4 + [f32] * 5 + [ctypes.POINTER(_AdamTensor), i32, vp, i64]
-                                       + [vp])
-    L.pgp_tune_forward_cells.argtypes = [i32] * 3 + [vp] * 5 + [vp]
-    L.pgp_forward1_many.argtypes = [i32] * 3 + [vp] * 13 + [vp]
-    for f in ("pgp_tune_step1_many", "pgp_adamw_table_many", "pgp_tune_forward_cells", "pgp_forward1_many"):
-        getattr(L, f).restype = i32
-    L.pgp_master_len.argtypes = [i32]
-    L.pgp_master_len.restype = ctypes.c_size_t
-    L._pgp_fleet_bound = True
-    return L
+bind_fleet = _native.bind   # the earlier helper's name: the previous release's tests reach the library through it
 
 
 def master_tensors(H: int) -> list:
@@ -1905,7 +1787,7 @@ class FleetTuner:
         self.device = torch.device("cuda" if device is None else device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self._L = L = bind_fleet(_native.lib())
+        self._L = L = _native.lib()
         self.lrs = dict(default_lrs(self.H), **(lrs or {}))
         self.wd, self.b1, self.b2, self.eps = weight_decay, betas[0], betas[1], eps
         self.sched = FleetSchedule(self.H, M, self.lrs["transformer"], betas)

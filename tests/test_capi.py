@@ -25,12 +25,12 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_every_ctypes_call_declares_argtypes():
-    """Every pgp_* entry point called through ctypes has argtypes set somewhere
-    in the package: without them ctypes passes Python ints as 32-bit C ints and
-    silently truncates device pointers (a GPU memory fault, not an error)."""
+    """Every pgp_* entry point called through ctypes has argtypes, from
+    ``_native.SIGNATURES`` or set where a profiling build's symbol is called:
+    ctypes would pass ints as 32-bit C ints and truncate device pointers."""
     import glob
     files = glob.glob("preganplus_amd/*.py") + glob.glob("tools/*.py") + glob.glob("tests/*.py") + ["bench.py"]
-    calls, decl = {}, set()
+    calls, decl = {}, set(_native.SIGNATURES)
     for f in files:
         s = open(f).read()
         for name in re.findall(r"\.(pgp_\w+)\(", s):

@@ -17,10 +17,7 @@ from preganplus_amd import train as TR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2
 NEW = ("pgp_tune_step1_many", "pgp_adamw_table_many", "pgp_tune_forward_cells", "pgp_forward1_many")
-
-
-def _lib():
-    return TR.bind_fleet(_native.lib())
+_lib = _native.lib
 
 
 def test_header_declares_and_library_exports():

@@ -1,8 +1,6 @@
 """The offline FPE training entry points report the host counts they are
 compiled for (csrc/pgp_fpetrain.hip: 16 and 50).  CPU: loads the library, makes
 no GPU call."""
-import ctypes
-
 import numpy as np
 
 from preganplus_amd import _native
@@ -10,10 +8,7 @@ from preganplus_amd import weights as W
 
 
 def _param_len(n):
-    L = _native.lib()
-    L.pgp_fpe_param_len.argtypes = [ctypes.c_int]
-    L.pgp_fpe_param_len.restype = ctypes.c_size_t
-    return int(L.pgp_fpe_param_len(n))
+    return int(_native.lib().pgp_fpe_param_len(n))
 
 
 def test_fpe_param_len_50_hosts():

@@ -18,17 +18,7 @@ OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2
 VP = ctypes.c_void_p
 NEW = ("pgp_gobi_train_steps_many", "pgp_gobi_train_eval_many", "pgp_gobi_create_many", "pgp_gobi_model_count",
        "pgp_gobi_set_model", "pgp_gobi_optimize_groups", "pgp_gobi_plan_groups")
-
-
-def _lib():
-    L = GT.bind_many(_native.lib())
-    L.pgp_gobi_plan_groups.argtypes = [ctypes.c_int, VP, ctypes.c_int, VP, ctypes.c_int]
-    L.pgp_gobi_plan_groups.restype = ctypes.c_int
-    L.pgp_gobi_create_many.argtypes = [ctypes.c_int, ctypes.c_int, VP, ctypes.c_size_t, ctypes.POINTER(VP)]
-    L.pgp_gobi_model_count.argtypes = [VP]
-    L.pgp_gobi_set_model.argtypes = [VP, ctypes.c_int, VP, ctypes.c_size_t]
-    L.pgp_gobi_optimize_groups.argtypes = [VP, ctypes.c_int, ctypes.c_int] + [VP] * 5 + [ctypes.c_int, VP, VP]
-    return L
+_lib = _native.lib
 
 
 def test_header_declares_and_library_exports():

@@ -2,7 +2,6 @@
 csrc/pgp_gobitrain.hip through pgp_capi.hip): declared, exported, and its
 argument checks, which run on the host before any launch.  CPU: loads the
 library, makes no GPU call."""
-import ctypes
 import os
 import re
 
@@ -12,16 +11,7 @@ from preganplus_amd import _native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2
-
-
-def _lib():
-    L = _native.lib()
-    vp, i32, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    L.pgp_gobi_train_steps.argtypes = [i32, i32, i32] + [vp] * 6 + [ctypes.c_longlong] + [dbl] * 5 + [vp, vp]
-    L.pgp_gobi_train_steps.restype = i32
-    L.pgp_gobi_train_eval.argtypes = [i32, i32, i32] + [vp] * 6
-    L.pgp_gobi_train_eval.restype = i32
-    return L
+_lib = _native.lib
 
 
 def _steps(L, H=16, N=4, n=0, step0=0, lr=1e-4, wd=1e-5, b1=0.9, b2=0.999, eps=1e-8, ptr=None):

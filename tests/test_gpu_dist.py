@@ -144,7 +144,6 @@ def _c3_run(sl, world):
     main = torch.cuda.Stream()
     side = torch.cuda.Stream()
     L = _native.lib()
-    L.pgp_tune_set_side_stream.argtypes = [ctypes.c_void_p]
     if world > 1:
         _native.check(L.pgp_tune_set_side_stream(ctypes.c_void_p(side.cuda_stream)), "pgp_tune_set_side_stream")
     try:

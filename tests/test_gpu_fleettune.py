@@ -316,7 +316,7 @@ def test_trainer_round_trip(H, p):
 @pytest.mark.parametrize("H", [8, 16])
 def test_refused_calls_leave_the_outputs_untouched(H):
     M, n, dev = 2, 2, "cuda"
-    L, vp = TR.bind_fleet(_native.lib()), ctypes.c_void_p
+    L, vp = _native.lib(), ctypes.c_void_p
     N, T = int(L.pgp_master_len(H)), 3
     f32, f64, i32 = torch.float32, torch.float64, torch.int32
     full = lambda shp, dt: torch.full(shp, SENT if dt != i32 else -7, dtype=dt, device=dev)

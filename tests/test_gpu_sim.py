@@ -2,7 +2,6 @@
 SURVEY §8f row f4) against the reference's own runSimulation outputs
 (tests/golden/sim_h*.npz, tests/golden/make_golden_sim.py) and the oracle
 (oracle/sim_oracle.py): integer/fp64 bookkeeping, so bit-exact."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -73,7 +72,6 @@ def test_simulate_python_power_semantics():
 def test_simulate_api_edges():
     from preganplus_amd import _native
     L = _native.lib()
-    L.pgp_simulate.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
     assert L.pgp_simulate(65, 1, 1, 1, 1, 1, 1, None) == -2
     assert L.pgp_simulate(16, 0, None, None, None, None, None, None) == 0
     assert L.pgp_simulate(16, 1, None, None, None, None, None, None) == -1

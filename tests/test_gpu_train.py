@@ -606,7 +606,6 @@ def test_reserved_cus_same_gradients(H):
     and the weight gradients are summed in other fp32 groupings; the gradients
     agree with the full-grid step to fp32 summation tolerance, and two reserved
     steps are bit-identical (still one fixed slab per workgroup)."""
-    import ctypes
     from preganplus_amd import _native
     from preganplus_amd import train as TR
     B = 1030
@@ -614,7 +613,6 @@ def test_reserved_cus_same_gradients(H):
     tr = TR.Trainer(H, w, max_batch=B)
     xs = torch.tensor(x, dtype=torch.float32)
     L = _native.lib()
-    L.pgp_tune_reserve_cus.argtypes = [ctypes.c_int]
 
     def grads(n):
         _native.check(L.pgp_tune_reserve_cus(n), "pgp_tune_reserve_cus")

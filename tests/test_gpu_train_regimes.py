@@ -159,13 +159,6 @@ def test_tuning_step_matches_autograd_in_regime(H, B, regime, tail):
     s.verify(s.run(), f"tune({H},{B})")
 
 
-def _bind_side_stream():
-    L = _native.lib()
-    L.pgp_tune_set_side_stream.argtypes = [ctypes.c_void_p]
-    L.pgp_tune_set_side_stream.restype = ctypes.c_int
-    return L
-
-
 def test_side_form_agrees_with_one_stream_form():
     """(b) (50, 657) on the library's side stream and, with the call's own
     stream named as the side stream, all on that one stream: the defer form
@@ -178,7 +171,7 @@ def test_side_form_agrees_with_one_stream_form():
     _assert_plan(TR.tune_plan_info(H, B), dict(bwd_side=1, fwd_side=1, dec_dws=2), "side form")
     s = _Step(H, B)
     own = torch.cuda.Stream(device=s.tr.device)   # a non-null handle (NULL selects the library's stream)
-    L = _bind_side_stream()
+    L = _native.lib()
     with torch.cuda.stream(own):
         g_side = s.run()
         try:

@@ -103,7 +103,6 @@ def test_plan_queries_answer_without_a_device():
     assert L.pgp_tune_plan_info(50, 500, 430, None, 11) == -1
     assert L.pgp_tune_plan_info(7, 4, 4, out, 11) == -2
     assert TR.gan_plan_info(16, 37) == 1 and TR.gan_plan_info(50, 1) > 1
-    L.pgp_gan_plan_info.argtypes = [ctypes.c_int, ctypes.c_int]
     assert L.pgp_gan_plan_info(7, 4) == -2 and L.pgp_gan_plan_info(50, 0) == -1
     with pytest.raises(_native.NativeError):
         TR.tune_plan_info(50, 500, fwd_batch=430)

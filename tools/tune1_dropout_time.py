@@ -17,7 +17,6 @@ Select the library with PGP_LIB to compare two builds, in alternating
 processes.  Prints one JSON line per host count.  There is no CPU path.
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -65,15 +64,7 @@ def measure(H, steps, replays, reps, p):
     sel = [t for t in tr.tensors if t["section"] == "transformer" and t["trainable"]]
     tab = torch.tensor(tr.adam_schedule_np("transformer", np.ones(steps, dtype=bool), ()), device=dev)
     words = torch.tensor(np.array([12345, 100], dtype=np.int64), device=dev)   # {seed, base step}
-    has_drop = hasattr(L, "pgp_tune_step1_dropout")
-    if has_drop:
-        dbl, vp, i32 = ctypes.c_double, ctypes.c_void_p, ctypes.c_int
-        L.pgp_tune_step1_dropout.argtypes = ([i32, i32] + [vp] * 6 + [dbl, dbl] + [vp] * 3
-                                             + [ctypes.c_float, vp, i32, vp])
-        L.pgp_tune_dropout_masks.argtypes = [i32, ctypes.c_float, vp, i32, vp, vp]
-        L.pgp_tune_dropout_mask_len.argtypes = [i32]
-        L.pgp_tune_dropout_mask_len.restype = ctypes.c_size_t
-        L.pgp_tune_step1_dropout.restype = L.pgp_tune_dropout_masks.restype = i32
+    has_drop = hasattr(L, "pgp_tune_step1_dropout")   # absent from a build before the dropout step (PGP_LIB)
 
     def step(i, drop):
         args = (H, K, win.data_ptr(), y.data_ptr(), c.data_ptr(), tr.P.data_ptr(), tr.G.data_ptr(), state.data_ptr(),
