@@ -195,14 +195,18 @@ def gan_split_flops_per_window(H: int, onehot: bool = True) -> int:
 
 
 def decoder_split_flops_per_window(H: int) -> int:
-    """bf16 MFMA flops K2b's split form executes per window: per (host, step)
-    chunk ceil(KS/8) blocks of 8 k-steps (KS = ceil(H/4) k-steps of 4), per
+    """bf16 MFMA flops K2b's split form executes per window.  A (host, step)
+    chunk is KS = ceil(H/4) k-steps of 4; where KS is no multiple of 8 the
+    chunks of a body (2 hosts x 3 steps at even H) form one k-step stream cut
+    into dense blocks of 8 (pgp_decoder.hip DecB: H = 50 has 25 bodies of
+    ceil(78/8) = 10 blocks), otherwise a chunk is KS/8 blocks.  Per block and
     16-row output tile (ceil(4H/16)) 6 v_mfma_f32_16x16x32_bf16 of
     16 x 16 x 32 x 2 flops, shared by the 16 windows of a wave."""
     ks = (H + 3) // 4
-    nb = ((ks + 3) // 4 + 1) // 2
+    cb = 1 if ks % 8 == 0 else W * (2 if H % 2 == 0 else 1)
+    blocks = H * W // cb * ((cb * ks + 7) // 8)
     mt = (4 * H + 15) // 16
-    return H * W * nb * mt * 6 * 16 * 16 * 32 * 2 // 16
+    return blocks * mt * 6 * 16 * 16 * 32 * 2 // 16
 
 
 def gan_flops_per_window(H: int) -> int:

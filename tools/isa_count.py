@@ -103,6 +103,42 @@ def encoder_asplit_counts(Hs=(50,), lib=LIB):
     return out
 
 
+def decoder_split_count(H=50, TW=2, lib=LIB):
+    """bf16 16x16x32 MFMAs of decoder_split_kernel<H, TW> (K2b's split form) as
+    built.  Its body loop is `#pragma unroll 1` and holds every MFMA, so this
+    is the count per body (pgp_decoder.hip DecB: CB chunks) and wave, a wave
+    covering TW window tiles."""
+    asm = _disasm(lib, "decoder_split_kernel")
+    m = re.search(rf"<_ZN3pgp12_GLOBAL__N_120decoder_split_kernelILi{H}ELi{TW}EEEvNS_7FwdArgsE>:\n(.*?)s_endpgm", asm,
+                  re.S)
+    if m is None:
+        raise RuntimeError(f"decoder_split_kernel<{H}, {TW}> not found in {lib}")
+    return len(re.findall(r"^\s+v_mfma_f32_16x16x32_bf16", m.group(1), re.M))
+
+
+def kernel_resources(needle, lib=LIB):
+    """{symbol: {vgpr_count, vgpr_spill_count, sgpr_spill_count,
+    private_segment_fixed_size}} from the code objects' metadata notes, for the
+    kernels of the BUILT library whose mangled name contains `needle`."""
+    keys = ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        shutil.copy(lib, os.path.join(td, "lib.so"))
+        subprocess.run([OBJDUMP, "--offloading", "lib.so"], cwd=td, check=True, capture_output=True)
+        for co in sorted(glob.glob(os.path.join(td, "lib.so.*gfx950"))):
+            notes = subprocess.run([os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf"), "--notes", co],
+                                   check=True, capture_output=True, text=True).stdout
+            # one "- .agpr_count: ..." list item per kernel
+            for item in re.split(r"\n\s+- \.", notes):
+                name = re.search(r"\.?name:\s+(\S+)", item)
+                if name is None or needle not in name.group(1) or ".vgpr_count" not in "." + item:
+                    continue
+                vals = {k: re.search(rf"\.?{k}:\s+(\d+)", item) for k in keys}
+                if all(vals.values()):
+                    out[name.group(1)] = {k: int(v.group(1)) for k, v in vals.items()}
+    return out
+
+
 _ASM_CACHE = {}
 
 
