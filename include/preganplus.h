@@ -572,6 +572,35 @@ int pgp_gan_step1(int n_hosts, const float* target, float* P, float* G, float* e
                   const pgp_adam_tensor* gen_tensors, int n_gen, const float* gen_sched, float* workspace,
                   float* probs_gen, float* probs_after, void* stream);
 
+/* The same two launches for a fleet of cells that each own a Gen / Disc (the
+ * reference keeps one GAN per PreGANPlusRecovery and trains it every interval,
+ * PreGANPlus.py:60-81, then gates its decision on the updated Disc,
+ * PreGANPlus.py:84-87), n_hosts 8 or 16, one workgroup per cell.  Per-cell
+ * arrays are contiguous slots: P / G / exp_avg / exp_avg_sq
+ * [n_cells][pgp_master_len(H)], emb [n_cells][2H], sched / ns [n_cells][H][H],
+ * target / probs / probs_gen / probs_after [n_cells][2], workspace
+ * [n_cells][pgp_gan_workspace_len(H, 1)].  Tensor offsets are relative to the
+ * slot and must lie in the disc / gen sections; cell c's AdamW table is at
+ * disc_sched + c * disc_sched_cell_stride floats ([n_disc][3] as
+ * pgp_adamw_table), likewise gen_sched.  active [n_cells] int32 or NULL (every
+ * cell); an inactive cell's slots and output rows are neither read nor written.
+ * Contract: cell m's outputs and its slots have the bits pgp_gan_forward1 /
+ * pgp_gan_step1 give on slot m's arrays, whatever n_cells, the cell's position
+ * and the other cells are.  The cells are grid x: no cap below INT_MAX.
+ * Before anything is enqueued: PGP_ERR_UNSUPPORTED for another host count;
+ * PGP_ERR_ARG for a negative count, a NULL array with n_cells > 0, n_disc /
+ * n_gen outside [0, 48], a negative stride or a tensor outside its section;
+ * n_cells == 0 is PGP_OK and launches nothing. */
+int pgp_gan_forward1_many(int n_hosts, int n_cells, const int* active, const float* emb, const float* sched,
+                          const float* P, float* workspace, float* ns, float* probs, void* stream);
+/* pgp_gan_step1 per active cell (PreGANPlus.py:60-81, the gate of PreGANPlus.py:84-87): see above. */
+int pgp_gan_step1_many(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
+                       float* exp_avg, float* exp_avg_sq, float lr_disc, float lr_gen, float weight_decay,
+                       float beta1, float beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
+                       const float* disc_sched, long long disc_sched_cell_stride, const pgp_adam_tensor* gen_tensors,
+                       int n_gen, const float* gen_sched, long long gen_sched_cell_stride, float* workspace,
+                       float* probs_gen, float* probs_after, void* stream);
+
 /* ---------------------------------------------------------------------------
  * The whole online training step of run_model in ONE call (BASELINE config
  * C3; replaces, per interval and for a batch of E environments, the sequence

@@ -126,6 +126,9 @@ SIGNATURES = {
     "pgp_adamw_table_many": (i32, [i32, i64, vp] + [vp] * 4 + [f32] * 5 + [adam, i32, vp, i64, stream]),
     "pgp_gan_forward1": (i32, [i32] + [vp] * 6 + [stream]),
     "pgp_gan_step1": (i32, [i32] + [vp] * 5 + [f32] * 6 + [adam, i32, vp] + [adam, i32, vp] + [vp] * 3 + [stream]),
+    "pgp_gan_forward1_many": (i32, [i32, i32] + [vp] * 7 + [stream]),
+    "pgp_gan_step1_many": (i32, [i32, i32] + [vp] * 6 + [f32] * 6 + [adam, i32, vp, i64] + [adam, i32, vp, i64]
+                           + [vp] * 3 + [stream]),
     "pgp_online_create": (i32, [ctypes.POINTER(_OnlineDesc), pvp]),
     "pgp_online_destroy": (i32, [vp]),
     "pgp_online_step": (i32, [vp, stream, stream, _COLL_FN, vp]),

@@ -880,6 +880,52 @@ int pgp_gan_step1(int n_hosts, const float* target, float* P, float* G, float* e
   return PGP_OK;
 }
 
+// ---- the fused GAN step for a fleet of cells, each on its own Gen / Disc (recovery/PreGANPlus.py:60-81 per
+// PreGANPlusRecovery, the gate of :84-87) ----  Every check runs before anything is enqueued.
+int pgp_gan_forward1_many(int n_hosts, int n_cells, const int* active, const float* emb, const float* sched,
+                          const float* P, float* workspace, float* ns, float* probs, void* stream) {
+  long tr, go, dof, all;
+  if (!gan1_supported(n_hosts) || !master_offsets(n_hosts, &tr, &go, &dof, &all))
+    return fail(PGP_ERR_UNSUPPORTED, "host count (fused GAN step for a fleet: 8 or 16)");
+  if (n_cells < 0) return fail(PGP_ERR_ARG, "n_cells >= 0");
+  if (n_cells == 0) return PGP_OK;
+  if (!emb || !sched || !P || !workspace || !ns || !probs) return fail(PGP_ERR_ARG, "bad gan_forward1_many arguments");
+  HIPCHK(launch_gan1_forward_cells(n_hosts, n_cells, active, emb, sched, P, workspace,
+                                   gan_workspace_floats(n_hosts, 1), ns, probs,
+                                   reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_gan_step1_many(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
+                       float* exp_avg, float* exp_avg_sq, float lr_disc, float lr_gen, float weight_decay,
+                       float beta1, float beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
+                       const float* disc_sched, long long disc_sched_cell_stride, const pgp_adam_tensor* gen_tensors,
+                       int n_gen, const float* gen_sched, long long gen_sched_cell_stride, float* workspace,
+                       float* probs_gen, float* probs_after, void* stream) {
+  long tr, go, dof, all;
+  if (!gan1_supported(n_hosts) || !master_offsets(n_hosts, &tr, &go, &dof, &all))
+    return fail(PGP_ERR_UNSUPPORTED, "host count (fused GAN step for a fleet: 8 or 16)");
+  if (n_cells < 0) return fail(PGP_ERR_ARG, "n_cells >= 0");
+  if (n_cells == 0) return PGP_OK;
+  if (!target || !P || !G || !exp_avg || !exp_avg_sq || !workspace || !probs_gen || !probs_after)
+    return fail(PGP_ERR_ARG, "bad gan_step1_many arguments");
+  if (n_disc < 0 || n_disc > kMaxTensors || n_gen < 0 || n_gen > kMaxTensors || (n_disc > 0 && !disc_tensors) ||
+      (n_gen > 0 && !gen_tensors) || !disc_sched || !gen_sched)
+    return fail(PGP_ERR_ARG, "AdamW tensor counts or tables");
+  if (disc_sched_cell_stride < 0 || gen_sched_cell_stride < 0) return fail(PGP_ERR_ARG, "negative table stride");
+  const pgp_adam_tensor none{};
+  AdamArgs ad, ag;  // offsets relative to the slot, inside the disc / gen sections
+  if (!adam_args(&ad, P, G, exp_avg, exp_avg_sq, lr_disc, weight_decay, beta1, beta2, eps,
+                 disc_tensors ? disc_tensors : &none, n_disc, disc_sched, dof, all) ||
+      !adam_args(&ag, P, G, exp_avg, exp_avg_sq, lr_gen, weight_decay, beta1, beta2, eps,
+                 gen_tensors ? gen_tensors : &none, n_gen, gen_sched, go, dof))
+    return fail(PGP_ERR_ARG, "AdamW tensor outside its section (disc / gen) of the slot");
+  HIPCHK(launch_gan1_step_cells(n_hosts, n_cells, active, target, workspace, gan_workspace_floats(n_hosts, 1), ad, ag,
+                                (long)disc_sched_cell_stride, (long)gen_sched_cell_stride, probs_gen, probs_after,
+                                reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
 int pgp_gan_probs(int n_hosts, int batch, const float* workspace, float* probs, void* stream) {
   if (!supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count");
   if (batch < 0 || (batch > 0 && (!workspace || !probs))) return fail(PGP_ERR_ARG, "bad arguments");

@@ -150,6 +150,15 @@ hipError_t launch_gan1_forward(int H, const float* emb, const float* sched, cons
 hipError_t launch_gan1_step(int H, const float* target, float* Pg, float* Pd, float* Gg, float* Gd, float* row,
                             const AdamArgs& ad, const AdamArgs& ag, float* probs_gen, float* probs_after,
                             hipStream_t st);
+// the same two for a fleet of cells, one workgroup per cell (pgp_gan1_cells.hip): cell b works on slot b of
+// emb [cells][2H], sched / ns [cells][H^2], P / G / moments [cells][master len] (ad / ag name slot 0), row
+// [cells][row_stride], target / probs* [cells][2], with the AdamW rows a.sched + b * stride; active [cells] or NULL
+hipError_t launch_gan1_forward_cells(int H, int n_cells, const int* active, const float* emb, const float* sched,
+                                     const float* P, float* row, long row_stride, float* ns, float* probs,
+                                     hipStream_t st);
+hipError_t launch_gan1_step_cells(int H, int n_cells, const int* active, const float* target, float* row,
+                                  long row_stride, const AdamArgs& ad, const AdamArgs& ag, long strideD, long strideG,
+                                  float* probs_gen, float* probs_after, hipStream_t st);
 
 // GAN step (pgp_gantrain.hip); ws = gan_workspace_floats(H, B) floats
 // logits != nullptr: the embedding is run_model's mask of logits / protos

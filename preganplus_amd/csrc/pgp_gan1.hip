@@ -19,7 +19,13 @@
 // device table of per-tensor (active, step_size, bc2_sqrt).  The window's
 // activations are also written to the GAN scratch row 0 (the layout
 // pgp_gantrain.hip uses, TGeo GS_*), so gan_probs / the eager kernels can follow.
+//
+// Both kernels also have a cell-indexed form (template parameter CELLS: one
+// workgroup per cell of a fleet, each on its own Gen / Disc), instantiated and
+// launched from pgp_gan1_cells.hip.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "pgp_device.hpp"
 #include "pgp_gemm.hpp"
@@ -143,16 +149,45 @@ PGP_DEV void g1_load_inputs(float* s, const float* __restrict__ emb, const float
   __syncthreads();
 }
 
-template <int H>
+// CELLS (pgp_gan_forward1_many / pgp_gan_step1_many): the cell-indexed form.
+// Workgroup b is cell b and works on slot b of every per-cell array (emb
+// [cells][2H], sched / ns [cells][H^2], P / G / moments [cells][TGeo<H>::ALL] —
+// Pg / Pd / Gg / Gd name slot 0's sections —, row [cells][row_stride], target /
+// probs [cells][2]; offsets in 64 bits): the pointers move to the slot, then the
+// same statements run.  An inactive cell leaves before any barrier and before
+// it touches its slot (uniform over the workgroup).  No atomics, no workgroup
+// waits for another, the slots are disjoint; G1<H>::TOTAL floats of LDS (~7 KB
+// at 16 hosts), so several cells share a CU and more cells than the device
+// holds at once queue.
+struct G1CellArgs {
+  const int* active;            // [cells] or nullptr: every cell
+  long row_stride;              // floats per cell of the workspace
+  long sched_d, sched_g;        // floats per cell of the disc / gen AdamW tables (step kernel)
+};
+template <bool CELLS>
+using G1Cell = std::conditional_t<CELLS, G1CellArgs, int>;
+
+template <int H, bool CELLS = false>
 __global__ __launch_bounds__(kG1Threads) void gan1_forward_kernel(const float* __restrict__ emb,
                                                                   const float* __restrict__ sched,
                                                                   const float* __restrict__ Pg,
                                                                   const float* __restrict__ Pd, float* __restrict__ row,
                                                                   float* __restrict__ ns_out,
-                                                                  float* __restrict__ probs) {
+                                                                  float* __restrict__ probs, G1Cell<CELLS> cell) {
   using L = G1<H>;
   __shared__ float s[L::TOTAL];
   const int tid = threadIdx.x;
+  if constexpr (CELLS) {
+    const long b = blockIdx.x;
+    if (cell.active && !cell.active[b]) return;
+    emb += b * (2 * H);
+    sched += b * L::HH;
+    Pg += b * TGeo<H>::ALL;
+    Pd += b * TGeo<H>::ALL;
+    row += b * cell.row_stride;
+    ns_out += b * L::HH;
+    probs += b * 2;
+  }
   g1_load_inputs<H>(s, emb, sched, tid);
   g1_forward<H>(s, Pg, Pd, tid);
   g1_store_row<H>(s, row, tid);
@@ -170,16 +205,41 @@ PGP_DEV void g1_adamw(const AdamArgs& a, int tid) {
   }
 }
 
-template <int H>
+// the same on the slot that starts `slot` floats into a's four buffers, from the
+// cell's own table rows `sched` (adamw_elem_slot: the cell-indexed form)
+PGP_DEV void g1_adamw_slot(const AdamArgs& a, long slot, const float* sched, int tid) {
+  for (int t = 0; t < a.ntensors; ++t) {
+    const float* r = sched + 3 * t;
+    if (r[0] == 0.f) continue;
+    const float step_size = r[1], bc2_sqrt = r[2];
+    for (long i = tid; i < a.t[t].n; i += kG1Threads) adamw_elem_slot(a, slot, a.t[t].off + i, step_size, bc2_sqrt);
+  }
+}
+
+template <int H, bool CELLS = false>
 // Pg / Pd / Gg / Gd alias the AdamW arguments' P and G (no __restrict__)
 __global__ __launch_bounds__(kG1Threads) void gan1_step_kernel(const float* __restrict__ target, float* Pg,
                                                                float* Pd, float* Gg, float* Gd, float* row,
                                                                AdamArgs ad, AdamArgs ag, float* __restrict__ probs_gen,
-                                                               float* __restrict__ probs_after) {
+                                                               float* __restrict__ probs_after, G1Cell<CELLS> cell) {
   using G = TGeo<H>;
   using L = G1<H>;
   __shared__ float s[L::TOTAL];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  [[maybe_unused]] long slot = 0, b = 0;
+  if constexpr (CELLS) {  // cell b: ad / ag's AdamW runs on the slot from the cell's table rows
+    b = blockIdx.x;
+    if (cell.active && !cell.active[b]) return;
+    slot = b * G::ALL;
+    target += b * 2;
+    Pg += slot;
+    Pd += slot;
+    Gg += slot;
+    Gd += slot;
+    row += b * cell.row_stride;
+    probs_gen += b * 2;
+    probs_after += b * 2;
+  }
   // the forward's activations (gan1_forward_kernel, same inputs)
   for (int i = tid; i < L::GIN; i += kG1Threads) s[L::X + i] = row[G::GS_X + i];
   for (int i = tid; i < L::DIN; i += kG1Threads) s[L::Z + i] = row[G::GS_Z + i];
@@ -200,7 +260,8 @@ __global__ __launch_bounds__(kG1Threads) void gan1_step_kernel(const float* __re
   if (tid < 128) Gd[G::D_W2 + tid] = s[L::DO + tid / 64] * s[L::DD + (tid & 63)];
   if (tid < 2) Gd[G::D_B2 + tid] = s[L::DO + tid];
   __syncthreads();
-  g1_adamw(ad, tid);
+  if constexpr (CELLS) g1_adamw_slot(ad, slot, ad.sched + b * cell.sched_d, tid);
+  else g1_adamw(ad, tid);
   __syncthreads();
   // ---- Gen step (PreGANPlus.py:69-75): BCE(Disc'(s, ns), [0, 1]) back into Gen ----
   mv_long<64>(Pd + G::D_W1, L::DIN, Pd + G::D_B1, s + L::Z, L::DIN, s + L::DD, wv, lane);
@@ -234,7 +295,8 @@ __global__ __launch_bounds__(kG1Threads) void gan1_step_kernel(const float* __re
   }
   if (tid < 64) Gg[G::G_B1 + tid] = s[L::DH + tid];
   __syncthreads();
-  g1_adamw(ag, tid);
+  if constexpr (CELLS) g1_adamw_slot(ag, slot, ag.sched + b * cell.sched_g, tid);
+  else g1_adamw(ag, tid);
   __syncthreads();
   // ---- the updated GAN on the same inputs: recover_decision's gate ----
   g1_forward<H>(s, Pg, Pd, tid);
@@ -242,7 +304,14 @@ __global__ __launch_bounds__(kG1Threads) void gan1_step_kernel(const float* __re
   if (tid < 2) probs_after[tid] = s[L::DO + 2 + tid];
 }
 
+
 }  // namespace
+
+// The cell-indexed instantiations and their launches live in a translation unit
+// of their own (pgp_gan1_cells.hip includes this file with PGP_G1_CELLS_TU):
+// instantiated beside the single-cell kernels they would change how those are
+// compiled, so each unit instantiates one family only.
+#ifndef PGP_G1_CELLS_TU
 
 bool gan1_supported(int H) { return H == 8 || H == 16; }
 
@@ -250,10 +319,10 @@ hipError_t launch_gan1_forward(int H, const float* emb, const float* sched, cons
                                float* row, float* ns, float* probs, hipStream_t st) {
   switch (H) {
     case 8:
-      gan1_forward_kernel<8><<<1, kG1Threads, 0, st>>>(emb, sched, Pg, Pd, row, ns, probs);
+      gan1_forward_kernel<8><<<1, kG1Threads, 0, st>>>(emb, sched, Pg, Pd, row, ns, probs, 0);
       break;
     case 16:
-      gan1_forward_kernel<16><<<1, kG1Threads, 0, st>>>(emb, sched, Pg, Pd, row, ns, probs);
+      gan1_forward_kernel<16><<<1, kG1Threads, 0, st>>>(emb, sched, Pg, Pd, row, ns, probs, 0);
       break;
     default:
       return hipErrorInvalidValue;
@@ -266,15 +335,66 @@ hipError_t launch_gan1_step(int H, const float* target, float* Pg, float* Pd, fl
                             hipStream_t st) {
   switch (H) {
     case 8:
-      gan1_step_kernel<8><<<1, kG1Threads, 0, st>>>(target, Pg, Pd, Gg, Gd, row, ad, ag, probs_gen, probs_after);
+      gan1_step_kernel<8><<<1, kG1Threads, 0, st>>>(target, Pg, Pd, Gg, Gd, row, ad, ag, probs_gen, probs_after, 0);
       break;
     case 16:
-      gan1_step_kernel<16><<<1, kG1Threads, 0, st>>>(target, Pg, Pd, Gg, Gd, row, ad, ag, probs_gen, probs_after);
+      gan1_step_kernel<16><<<1, kG1Threads, 0, st>>>(target, Pg, Pd, Gg, Gd, row, ad, ag, probs_gen, probs_after, 0);
       break;
     default:
       return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+
+#else  // PGP_G1_CELLS_TU
+
+// one workgroup per cell on grid x (up to 2^31 - 1 cells: no cap of its own)
+hipError_t launch_gan1_forward_cells(int H, int n_cells, const int* active, const float* emb, const float* sched,
+                                     const float* P, float* row, long row_stride, float* ns, float* probs,
+                                     hipStream_t st) {
+  if (n_cells <= 0) return hipSuccess;
+  const G1CellArgs cell{active, row_stride, 0, 0};
+#define PGP_G1_FWD_CELLS(h)                                                                                  \
+  gan1_forward_kernel<h, true><<<n_cells, kG1Threads, 0, st>>>(emb, sched, P + TGeo<h>::OFF_GEN,            \
+                                                               P + TGeo<h>::OFF_DISC, row, ns, probs, cell)
+  switch (H) {
+    case 8:
+      PGP_G1_FWD_CELLS(8);
+      break;
+    case 16:
+      PGP_G1_FWD_CELLS(16);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef PGP_G1_FWD_CELLS
+  return hipGetLastError();
+}
+
+// ad / ag name slot 0 of P / G / the moments, their sched the first cell's table rows
+hipError_t launch_gan1_step_cells(int H, int n_cells, const int* active, const float* target, float* row,
+                                  long row_stride, const AdamArgs& ad, const AdamArgs& ag, long sched_d, long sched_g,
+                                  float* probs_gen, float* probs_after, hipStream_t st) {
+  if (n_cells <= 0) return hipSuccess;
+  const G1CellArgs cell{active, row_stride, sched_d, sched_g};
+#define PGP_G1_STEP_CELLS(h)                                                                                   \
+  gan1_step_kernel<h, true><<<n_cells, kG1Threads, 0, st>>>(                                                   \
+      target, ad.param + TGeo<h>::OFF_GEN, ad.param + TGeo<h>::OFF_DISC, ad.grad + TGeo<h>::OFF_GEN,          \
+      ad.grad + TGeo<h>::OFF_DISC, row, ad, ag, probs_gen, probs_after, cell)
+  switch (H) {
+    case 8:
+      PGP_G1_STEP_CELLS(8);
+      break;
+    case 16:
+      PGP_G1_STEP_CELLS(16);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef PGP_G1_STEP_CELLS
+  return hipGetLastError();
+}
+
+#endif  // PGP_G1_CELLS_TU
 
 }  // namespace pgp

@@ -38,6 +38,10 @@ FPE_16 encoder + K = 3 prototypes (HIP kernel K4), PreGAN's own Gen/Disc (K3),
 GAN-only online training when ``training``.  The GRU state is drawn exactly as
 the reference draws it (``torch.randn(1, 1, 3, dtype=double)`` on the CPU
 generator, ``models.py:70``), so a seeded run reproduces the reference's h0.
+
+``PreGANPlusFleetRecovery``: ``PreGANPlusRecovery.run_model``
+for M cells of 8 or 16 hosts at once, each on its own Transformer, Gen, Disc
+and prototypes (``train.FleetTuner``), each cell with the bits of a lone plugin.
 """
 from __future__ import annotations
 
@@ -856,3 +860,176 @@ class PreGANRecovery(_SaveGan, Recovery):
         if self.training:
             self.train_gan(embedding, schedule_data)
         return self.recover_decision(embedding, schedule_data, original_decision)
+
+
+class PreGANPlusFleetRecovery:
+    """``PreGANPlusRecovery.run_model`` (PreGANPlus.py:115-136) for a fleet of M
+    cells of one host count (8 or 16, ``TR.FUSED_STEP_HOSTS``), each with its
+    own Transformer, Gen, Disc, prototypes and optimizer state — the reference
+    keeps one of each per PreGANPlusRecovery — on ``TR.FleetTuner``'s slots.
+
+    weights / extras: per cell what ``PreGANPlusRecovery(weights=, extra=)``
+    takes (``extra["train_time_data"]`` included); dropout / dropout_seeds as
+    ``FleetTuner``.  ``setEnvironments(envs)`` binds M environment objects with
+    the fields the lone plugin reads (``stats.time_series`` / ``schedule_series``
+    / ``runSimulation``, ``scheduler.result_cache``, ``containerlist``);
+    ``run_model(original_decisions)`` returns M entries: per cell what the lone
+    plugin's ``run_model`` returns, or, where the lone plugin raises
+    ZeroDivisionError (no positive label in the cell's tuning windows), that
+    exception object — the cell's weights and state have advanced as the lone
+    plugin's do, and the other cells are unaffected.
+
+    One call: every cell's detect forward in one launch and one download;
+    cells without an anomaly keep their decision and are inactive from there
+    on; for the others the tuning graph(s) are launched on the tuning stream
+    (one ``tune`` per distinct dataset length, through the ``active`` mask),
+    ``FleetTuner.train_gan(simulate=...)`` runs on the cells'
+    ``env.stats.runSimulation`` meanwhile, the tuning is finished, and each
+    cell's decision is recovered with its own updated gate — the lone
+    plugin's order.  Per cell ``accuracy_list``, ``epoch``, ``classes`` and
+    ``hosts_from`` are kept as the lone plugin keeps them.
+
+    ``save_checkpoints(folder, m)`` writes cell m's three checkpoints through
+    ``FleetTuner.trainer(m)``.  The lone plugin's per-call asynchronous
+    ``save_gan`` writer is out of scope here and off: nothing is written
+    unless ``save_checkpoints`` is called."""
+
+    def __init__(self, hosts, weights, extras, training=False, dropout=0.0, dropout_seeds=None, device=None, env=""):
+        if hosts not in TR.FUSED_STEP_HOSTS:
+            raise ValueError(f"the fleet plugin runs the fused batch-1 steps: hosts in {TR.FUSED_STEP_HOSTS}, "
+                             f"not {hosts}")
+        weights = list(weights)
+        extras = [e or {} for e in (extras if extras is not None else [None] * len(weights))]
+        if len(extras) != len(weights):
+            raise ValueError(f"extras: {len(extras)} entries for {len(weights)} cells")
+        self.hosts, self.training = hosts, training
+        self.env_name = "simulator" if env == "" else "framework"
+        self.model_name, self.gen_name, self.disc_name = f"Transformer_{hosts}", f"Gen_{hosts}", f"Disc_{hosts}"
+        self.tuner = TR.FleetTuner(hosts, weights, extras, dropout=dropout, dropout_seeds=dropout_seeds,
+                                   device=device)
+        self.M = M = self.tuner.M
+        self.device = self.tuner.device
+        self.extras = extras
+        self.epoch = [int(e.get("meta/gen/epoch", 0)) for e in extras]
+        self.accuracy_list = [W.accuracy_list_from_arrays(e, "meta/gen/accuracy_list") for e in extras]
+        self.model_epoch = [int(e.get("meta/transformer/epoch", ep)) for e, ep in zip(extras, self.epoch)]
+        self.model_accuracy_list = [W.accuracy_list_from_arrays(e, "meta/transformer/accuracy_list") for e in extras]
+        self.train_time_data = []
+        for e in extras:
+            if "train_time_data" in e:
+                self.train_time_data.append(np.asarray(e["train_time_data"], dtype=np.float64))
+            else:
+                self.train_time_data.append(
+                    np.load(os.path.join("recovery/PreGANSrc/data", self.env_name, "time_series.npy")))
+        self.classes = [None] * M
+        self.hosts_from = [None] * M
+        self.envs = None
+        self._tune_stream = None
+        self._rio = None
+
+    def setEnvironments(self, envs):
+        envs = list(envs)
+        if len(envs) != self.M:
+            raise ValueError(f"{len(envs)} environments for {self.M} cells")
+        self.envs = envs
+
+    @property
+    def prototypes(self):
+        """Per cell the tuning state's prototypes [K,2]."""
+        return [s.protos for s in self.tuner.states]
+
+    def _input_window(self, m):   # PreGANPlus.py:107-113
+        td = TR.normalize_test_time_data(self.envs[m].stats.time_series, self.train_time_data[m])
+        if td.shape[0] >= 3:
+            td = td[-3:]
+        return TR.convert_to_windows(td)[-1]
+
+    def _score(self, m):
+        def score(schedule):      # utils.py:97-100
+            e, r = self.envs[m].stats.runSimulation(torch.tensor(schedule))
+            return COEFF_ENERGY * e + COEFF_LATENCY * r
+        return score
+
+    def run_model(self, original_decisions):
+        ft, M, H = self.tuner, self.M, self.hosts
+        original_decisions = list(original_decisions)
+        if self.envs is None or len(original_decisions) != M:
+            raise ValueError(f"run_model: setEnvironments first, and one original decision per cell ({M})")
+        scheds = np.stack([np.asarray(e.scheduler.result_cache, dtype=np.float64) for e in self.envs])
+        wins = np.stack([self._input_window(m) for m in range(M)])
+        out = ft.detect_numpy(wins, scheds)
+        act = out["any"].astype(bool).copy()
+        res = list(original_decisions)       # no anomaly: the original decision (PreGANPlus.py:119-127)
+        if not act.any():
+            return res
+        cells = np.flatnonzero(act)
+        anom = out["logits"][:, :, 1] > out["logits"][:, :, 0]
+        emb = np.where(anom[:, :, None], out["protos"], 0.0).astype(np.float32)
+        final_target = {}
+        for m in cells:
+            self.classes[m] = out["cls"][m].tolist()
+            final_target[m] = out["final_target"][m].tolist()
+        # the tuning graphs first, on their own stream (they share no data with the GAN step), one
+        # tune() per distinct dataset length; then train_gan around the host simulators; the tuning's
+        # host bookkeeping and accuracy_list entry after train_gan's, in the reference's order
+        data = {m: TR.on_the_fly_dataset(self.envs[m].stats.time_series, self.envs[m].stats.schedule_series,
+                                         self.train_time_data[m]) for m in cells}
+        groups = {}
+        for m in cells:
+            groups.setdefault(np.asarray(data[m][0]).shape[0], []).append(m)
+        cur = torch.cuda.current_stream(self.device)
+        if self._tune_stream is None:
+            self._tune_stream = torch.cuda.Stream(self.device)
+        self._tune_stream.wait_stream(cur)   # the detect forward read the weights the tuning updates
+        pending = []
+        try:
+            for n, ms in groups.items():
+                w = np.zeros((M, n, 3, 3 * H), dtype=np.float32)
+                y = np.zeros((M, n, H), dtype=np.int32)
+                c = np.zeros((M, n, H), dtype=np.int32)
+                on = np.zeros(M, dtype=bool)
+                for m in ms:
+                    w[m], y[m], c[m] = data[m][0], np.asarray(data[m][2]).reshape(n, H), \
+                        np.asarray(data[m][3]).reshape(n, H)
+                    on[m] = True
+                pending.append((ms, ft.tune_launch(w, y, c, on, score=True, stream=self._tune_stream)))
+            gan = ft.train_gan(emb, scheds, simulate=[self._score(m) for m in range(M)], active=act)
+            for m in cells:                  # PreGANPlus.py:76-77
+                self.epoch[m] += 1
+                self.accuracy_list[m].append((gan[m][3], gan[m][4]))
+        finally:
+            tuned = []
+            for ms, finish in pending:       # a launched tuning step is completed and recorded even if train_gan raised
+                tuned.append((ms, finish()))
+            cur.wait_stream(self._tune_stream)
+            if len(tuned) > 1:
+                ft.sync_state_rows([m for ms, _ in tuned[:-1] for m in ms])
+        for ms, r in tuned:
+            for m in ms:
+                losses, scores = r[m]
+                if scores is None:           # the lone plugin raises here, after the update (train.py:109)
+                    res[m] = ft.tune_errors[m]
+                    continue
+                loss = float(np.mean([a for a, _ in losses]) + np.mean([t for _, t in losses]))   # train.py:56-57
+                factor = ft.states[m].factor + TR.PROTO_UPDATE_MIN
+                self.accuracy_list[m].append((loss, factor, scores[0], scores[1]))                # :58
+        if self._rio is None:
+            self._rio = _RecoverIO(H, self.device)
+        for m in cells:                      # PreGANPlus.py:83-105, each cell on its own updated gate
+            if isinstance(res[m], ZeroDivisionError):
+                continue
+            p = ft.gan_probs_after[m]
+            res[m], hf = _recover(self.envs[m], H, scheds[m], original_decisions[m], bool(p[0] > p[1]), self.device,
+                                  final_target[m], io=self._rio)
+            if hf is not None:
+                self.hosts_from[m] = hf
+        return res
+
+    # -- utils.py:49-58 per cell: the explicit full save of PreGANPlusRecovery.save_checkpoints --
+    def save_checkpoints(self, folder, m):
+        tr, st = self.tuner.trainer(m)
+        save_checkpoints(tr, folder, self.env_name, self.model_epoch[m], self.model_accuracy_list[m],
+                         [("transformer", self.model_name, st.protos)])
+        save_checkpoints(tr, folder, self.env_name, self.epoch[m], self.accuracy_list[m],
+                         [("gen", self.gen_name, None)])
+        save_checkpoints(tr, folder, self.env_name, 0, [], [("disc", self.disc_name, None)])

@@ -1646,11 +1646,14 @@ class FleetSchedule:
     call by ``Trainer.adam_schedule_np``'s rule, for all cells at once.  No
     device."""
 
-    def __init__(self, H: int, n_cells: int, lr: float | None = None, betas=(0.9, 0.999)):
+    def __init__(self, H: int, n_cells: int, lr: float | None = None, betas=(0.9, 0.999), lrs: dict | None = None):
         self.H, self.M = int(H), int(n_cells)
         self.tensors = master_tensors(self.H)
-        self.lr = default_lrs(self.H)["transformer"] if lr is None else lr
+        self.lrs = dict(default_lrs(self.H), **(lrs or {}))   # the GAN sections' rates (gan_tables)
+        self.lr = self.lrs["transformer"] if lr is None else lr
         self.b1, self.b2 = betas
+        self.sel_disc = [i for i, t in enumerate(self.tensors) if t["section"] == "disc" and t["trainable"]]
+        self.sel_gen = [i for i, t in enumerate(self.tensors) if t["section"] == "gen" and t["trainable"]]
         self.sel = [i for i, t in enumerate(self.tensors) if t["section"] == "transformer" and t["trainable"]]
         self.cond = np.array([self.tensors[i]["name"] in COND_TENSORS for i in self.sel])
         self.base_col = next(i for i, t in enumerate(self.tensors)
@@ -1683,6 +1686,27 @@ class FleetSchedule:
             self.steps[:, self.sel] = steps[:, -1, :]
         return tab
 
+    def gan_tables(self, active=None):
+        """One ``train_gan`` call's AdamW tables (tabD [M,nD,3], tabG [M,nG,3])
+        fp32 over the Disc's and the Gen's trainable tensors: per active cell
+        the rows ``Trainer.adam_schedule_np(section, [True], ())`` gives with
+        ``lrs["disc"]`` / ``lrs["gen"]``; advances those counts by the one
+        step.  An inactive cell's rows are zero, its counts stay; the
+        transformer's counts are not touched."""
+        act = np.ones(self.M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(self.M)
+        out = []
+        for sel, lr in ((self.sel_disc, self.lrs["disc"]), (self.sel_gen, self.lrs["gen"])):
+            steps = self.steps[:, sel] + act[:, None]
+            st = np.maximum(steps, 1.0)
+            tab = np.empty(steps.shape + (3,), dtype=np.float32)
+            tab[..., 0] = 1.0
+            tab[..., 1] = lr / (1 - self.b1 ** st)
+            tab[..., 2] = np.sqrt(1 - self.b2 ** st)
+            tab[~act] = 0.0
+            self.steps[:, sel] = steps
+            out.append(tab)
+        return out[0], out[1]
+
 
 def fleet_staging_layout(H: int, n_cells: int, n: int, K: int, n_tensors: int):
     """The input staging of one ``FleetTuner.tune`` call, uploaded with one
@@ -1692,6 +1716,12 @@ def fleet_staging_layout(H: int, n_cells: int, n: int, K: int, n_tensors: int):
     parts = [("W", np.float32, (M, n, 3, 3 * H)), ("Y", np.int32, (M, n, H)), ("C", np.int32, (M, n, H)),
              ("sched", np.float32, (M, n, n_tensors, 3)), ("active", np.int32, (M,)),
              ("state", np.float64, (M, 2 * K + 3)), ("rng", np.int64, (M, 2))]
+    return _aligned_layout(parts)
+
+
+def _aligned_layout(parts):
+    """[(name, dtype, shape)] -> ([(name, dtype, shape, byte offset, bytes)], total
+    bytes), every part 8-byte aligned."""
     off, lay = 0, []
     for name, dt, shp in parts:
         nb = int(np.prod(shp)) * np.dtype(dt).itemsize
@@ -1699,6 +1729,32 @@ def fleet_staging_layout(H: int, n_cells: int, n: int, K: int, n_tensors: int):
         lay.append((name, dt, shp, off, nb))
         off += nb
     return lay, (off + 7) // 8 * 8
+
+
+def fleet_gan_staging_layout(H: int, n_cells: int, n_disc: int, n_gen: int, envs: bool = False):
+    """The input staging of one ``FleetTuner.train_gan`` call, in
+    ``fleet_staging_layout``'s form.  ``simulate=`` mode uploads [emb .. active]
+    before the forward graph and [active .. tabG] before the step graph (one
+    copy each); ``envs=`` mode has the packed records last and uploads the
+    whole buffer once (its target part is written on the device)."""
+    M = n_cells
+    parts = [("emb", np.float32, (M, 2 * H)), ("sched", np.float32, (M, H, H)), ("active", np.int32, (M,)),
+             ("target", np.float32, (M, 2)), ("tabD", np.float32, (M, n_disc, 3)), ("tabG", np.float32, (M, n_gen, 3))]
+    if envs:
+        parts.append(("envs", np.float64, (M, 2 + 20 * H)))   # simulate.env_len(H)
+    return _aligned_layout(parts)
+
+
+def fleet_gan_output_layout(H: int, n_cells: int, envs: bool = False):
+    """The output gather of one ``FleetTuner.train_gan`` call: the forward's
+    [ns, probs] (downloaded after graph A), the step's [probs_gen, probs_after]
+    (after graph B) and, in ``envs=`` mode, ``pgp_simulate``'s fp64 rows."""
+    M = n_cells
+    parts = [("ns", np.float32, (M, H, H)), ("probs", np.float32, (M, 2)), ("probs_gen", np.float32, (M, 2)),
+             ("probs_after", np.float32, (M, 2))]
+    if envs:
+        parts.append(("sim", np.float64, (M, 4)))
+    return _aligned_layout(parts)
 
 
 _NP2TORCH = {np.float32: torch.float32, np.int32: torch.int32, np.float64: torch.float64, np.int64: torch.int64}
@@ -1749,13 +1805,85 @@ class _FleetGraph:
             self.issue(ft)
 
 
+class _FleetGanGraph:
+    """One ``FleetTuner.train_gan`` call's buffers and captured graphs, for
+    every cell at once (``_GanGraph`` for a fleet).  ``simulate=`` mode: graph
+    A is one ``pgp_gan_forward1_many`` launch, graph B one
+    ``pgp_gan_step1_many`` launch, around the host simulators.  ``envs=`` mode:
+    ONE graph, forward -> ``pgp_simulate`` on the device's ns and sched
+    buffers -> step; the target stays on the device.  Inputs in one pinned
+    staging buffer (``fleet_gan_staging_layout``), outputs in one gather
+    (``fleet_gan_output_layout``), every part 8-byte aligned."""
+
+    def __init__(self, ft: "FleetTuner", envs: bool):
+        H, M, dev = ft.H, ft.M, ft.device
+        self.device_sim = bool(envs)    # envs= mode: the records are a staging part, scored on the device
+        lay, total = fleet_gan_staging_layout(H, M, len(ft.selD), len(ft.selG), envs)
+        olay, ototal = fleet_gan_output_layout(H, M, envs)
+        self.din = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self.dout = torch.zeros(ototal, dtype=torch.uint8, device=dev)
+        self.hout = torch.zeros(ototal, dtype=torch.uint8).pin_memory()
+        self.hviews, self.oviews, self.span, self.ospan = {}, {}, {}, {}
+        for name, dt, shp, o, nb in lay:
+            setattr(self, name, self.din[o:o + nb].view(_NP2TORCH[dt]).view(shp))
+            self.hviews[name] = self.hin[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
+            self.span[name] = (o, o + nb)
+        for name, dt, shp, o, nb in olay:
+            setattr(self, name, self.dout[o:o + nb].view(_NP2TORCH[dt]).view(shp))
+            self.oviews[name] = self.hout[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
+            self.ospan[name] = (o, o + nb)
+        self.ws_len = int(ft._L.pgp_gan_workspace_len(H, 1))
+        self.gscr = torch.zeros((M, self.ws_len), dtype=torch.float32, device=dev)
+        self.graphs = None
+
+    def issue(self, ft: "FleetTuner", part: str):
+        """The launches of graph ``part`` ("A", "B", or "E": the envs= graph) on the current stream."""
+        if part in ("A", "E"):
+            ft.gan_forward_many(self)
+        if part == "E":
+            _native.check(ft._L.pgp_simulate(ft.H, ft.M, self.envs.data_ptr(), self.ns.data_ptr(),
+                                             self.sched.data_ptr(), self.sim.data_ptr(), self.target.data_ptr(),
+                                             ft._stream()), "pgp_simulate")
+        if part in ("B", "E"):
+            ft.gan_step_many(self)
+
+    def capture(self, ft: "FleetTuner"):
+        torch.cuda.synchronize(ft.device)
+        self.graphs = {}
+        for part in (("E",) if self.device_sim else ("A", "B")):
+            g = self.graphs[part] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self.issue(ft, part)
+
+    def run(self, ft: "FleetTuner", part: str):
+        """Replay graph ``part`` (issue its launches eagerly if ``ft.gan_capture`` is off)."""
+        if not ft.gan_capture:
+            return self.issue(ft, part)
+        if self.graphs is None:
+            self.capture(ft)
+        self.graphs[part].replay()
+
+    def upload(self, first: str, last: str):
+        a, b = self.span[first][0], self.span[last][1]
+        self.din[a:b].copy_(self.hin[a:b], non_blocking=True)
+
+    def download(self, ft: "FleetTuner", first: str, last: str):
+        a, b = self.ospan[first][0], self.ospan[last][1]
+        self.hout[a:b].copy_(self.dout[a:b], non_blocking=True)
+        torch.cuda.current_stream(ft.device).synchronize()
+
+
 class FleetTuner:
     """M decision models of one host count in contiguous device slots, tuned
     together: what M ``Trainer`` + ``TuneState`` pairs running ``backprop``
     one after another compute, bit for bit per cell, in one graph of 2n + 1
     launches (``pgp_tune_step1_many`` / ``pgp_adamw_table_many`` /
     ``pgp_tune_forward_cells``), and the per-interval forward of every cell in
-    one launch (``pgp_forward1_many``).  8 or 16 hosts (``FUSED_STEP_HOSTS``).
+    one launch (``pgp_forward1_many``).  ``train_gan`` is the lone
+    ``train_gan`` for every cell on its own Gen / Disc, two launches for all
+    cells (``pgp_gan_forward1_many`` / ``pgp_gan_step1_many``), bit for bit
+    per cell as well.  8 or 16 hosts (``FUSED_STEP_HOSTS``).
 
     weights: M weight dicts (``weights.synth_weights``' form; every cell the
     same number of prototypes); extras: per cell ``Trainer``'s ``extra``
@@ -1790,7 +1918,7 @@ class FleetTuner:
         self._L = L = _native.lib()
         self.lrs = dict(default_lrs(self.H), **(lrs or {}))
         self.wd, self.b1, self.b2, self.eps = weight_decay, betas[0], betas[1], eps
-        self.sched = FleetSchedule(self.H, M, self.lrs["transformer"], betas)
+        self.sched = FleetSchedule(self.H, M, self.lrs["transformer"], betas, lrs=self.lrs)
         self.tensors = self.sched.tensors
         self.sel = [self.tensors[i] for i in self.sched.sel]
         self.slot_len = n = int(L.pgp_master_len(self.H))
@@ -1823,6 +1951,15 @@ class FleetTuner:
         self._desc = (_AdamTensor * len(self.sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in self.sel])
         self._graphs = {}
         self._detect_io = None
+        self.tune_errors = {}       # cell -> the ZeroDivisionError its last scored tune() met (results)
+        # the per-cell GAN step (train_gan): the Disc's / Gen's trainable tensors, offsets relative to the slot
+        self.selD = [self.tensors[i] for i in self.sched.sel_disc]
+        self.selG = [self.tensors[i] for i in self.sched.sel_gen]
+        desc = lambda sel: (_AdamTensor * len(sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in sel])
+        self._descD, self._descG = desc(self.selD), desc(self.selG)
+        self._gan_graphs = {}
+        self.gan_capture = True     # False: train_gan issues its launches eagerly (the tests hold both equal)
+        self.gan_probs_after = np.zeros((M, 2), dtype=np.float32)
 
     def _stream(self):
         idx = self.device.index
@@ -1907,10 +2044,15 @@ class FleetTuner:
                 continue
             lg = out[g.o_lg:g.o_pr].reshape(M, n, H, 2)[c]
             pr = out[g.o_pr:].reshape(M, n, H, 2)[c]
+            self.tune_errors.pop(c, None)
             try:
                 scores = accuracy_scores(lg, pr, anom[c], cls[c], self.states[c].protos)
-            except ZeroDivisionError:   # no window of the cell has a positive label: the lone call raises here
-                scores = None           # (train.py:109); one such cell must not stop the fleet
+            except ZeroDivisionError as e:   # no window of the cell has a positive label: the lone call raises here
+                scores = None                # (train.py:109); one such cell must not stop the fleet
+                # the exception the lone call raises, for a caller that hands it on; without its traceback,
+                # whose frame names this tuner: kept, it would tie the tuner into a reference cycle and leave
+                # its graphs and pinned buffers to the cyclic collector, which may run inside a later capture
+                self.tune_errors[c] = e.with_traceback(None)
             res[c] = (losses, scores)
         return res
 
@@ -1923,16 +2065,129 @@ class FleetTuner:
         window), None for the others, whose slots and counts stay untouched.
         One upload from pinned staging (``active`` among the inputs: one graph
         serves any subset), one graph replay, one download."""
+        return self.tune_launch(wins, anom, cls, active, score)()
+
+    def tune_launch(self, wins, anom, cls, active=None, score: bool = True, stream=None):
+        """``tune`` up to its device work, launched on ``stream`` (default: the
+        current one); returns the function that waits for it and returns what
+        ``tune`` would (``backprop``'s ``defer``, for a fleet: the fleet plugin
+        overlaps the tuning graph with train_gan's host simulators).  Calls
+        with disjoint ``active`` sets and different window counts may be
+        launched before any is finished; finish them in launch order, then
+        ``sync_state_rows`` if more than one was in flight."""
         n = np.asarray(wins).shape[1]
         if n == 0:
-            return [(([], None) if score else []) for _ in range(self.M)]
+            res = [(([], None) if score else []) for _ in range(self.M)]
+            return lambda: res
         g = self.graph(n, score)
         anom, cls, act = self.stage(g, wins, anom, cls, active)
-        g.din.copy_(g.hin, non_blocking=True)
-        g.graph.replay()
-        g.hout.copy_(g.dout, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return self.results(g, g.hout.numpy(), anom, cls, act)
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.stream(st):
+            g.din.copy_(g.hin, non_blocking=True)
+            g.graph.replay()
+            g.hout.copy_(g.dout, non_blocking=True)
+
+        def finish():
+            st.synchronize()
+            return self.results(g, g.hout.numpy(), anom, cls, act)
+
+        return finish
+
+    def sync_state_rows(self, cells):
+        """Rewrite the rows of ``cells`` in the device state from the host
+        states: after overlapped ``tune_launch`` calls the device state is the
+        last call's buffer, where cells tuned by an earlier call still hold
+        the rows they were staged with."""
+        for c in cells:
+            self.state_dev[c].copy_(torch.from_numpy(self.states[c].vector()))
+
+    # ---------------- the per-cell GAN step ----------------
+    def gan_forward_many(self, g: _FleetGanGraph):
+        """Gen + Disc forward of every active cell on its own GAN (``pgp_gan_forward1_many``)."""
+        _native.check(self._L.pgp_gan_forward1_many(
+            self.H, self.M, g.active.data_ptr(), g.emb.data_ptr(), g.sched.data_ptr(), self.P.data_ptr(),
+            g.gscr.data_ptr(), g.ns.data_ptr(), g.probs.data_ptr(), self._stream()), "pgp_gan_forward1_many")
+
+    def gan_step_many(self, g: _FleetGanGraph):
+        """The rest of train_gan for every active cell from its own table rows (``pgp_gan_step1_many``)."""
+        _native.check(self._L.pgp_gan_step1_many(
+            self.H, self.M, g.active.data_ptr(), g.target.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
+            self.m.data_ptr(), self.v.data_ptr(), self.lrs["disc"], self.lrs["gen"], self.wd, self.b1, self.b2,
+            self.eps, self._descD, len(self.selD), g.tabD.data_ptr(), 3 * len(self.selD),
+            self._descG, len(self.selG), g.tabG.data_ptr(), 3 * len(self.selG),
+            g.gscr.data_ptr(), g.probs_gen.data_ptr(), g.probs_after.data_ptr(), self._stream()),
+            "pgp_gan_step1_many")
+
+    def gan_graph(self, envs: bool = False) -> _FleetGanGraph:
+        """train_gan's buffers and graphs, cached per mode (captured on first use)."""
+        g = self._gan_graphs.get(bool(envs))
+        if g is None:
+            g = self._gan_graphs[bool(envs)] = _FleetGanGraph(self, bool(envs))
+        return g
+
+    def train_gan(self, emb, scheds, simulate=None, envs=None, active=None):
+        """``train_gan`` (PreGANPlus.py:60-81) for every active cell on its own
+        Gen / Disc: emb [M,H,2] (or [M,2H]), scheds [M,H,H], active [M] (None:
+        all).  Exactly one of
+
+          simulate: M callables (schedule ndarray -> score), the plugin's host
+            runSimulation.  Graph A (one upload, ``pgp_gan_forward1_many``, one
+            download), then each active cell's two simulator calls in cell
+            order, the new schedule first, then graph B (one upload of targets,
+            tables and ``active``, ``pgp_gan_step1_many``, one download);
+          envs: [M, simulate.env_len(H)] packed records, scored by
+            ``pgp_simulate`` inside ONE graph (forward -> simulate -> step)
+            with no host round trip.  An inactive cell's record is not used
+            (zeros are staged in its place); its ns rows stay what they were.
+
+        Returns a list of M entries: (ns, new_score, orig_score, gen_loss,
+        disc_loss) as the lone ``train_gan`` returns them, None for an
+        inactive cell, whose slots, counts and output rows stay untouched.
+        ``self.gan_probs_after`` [M,2] holds the updated GANs' gates
+        (PreGANPlus.py:84-87) of the active cells."""
+        if (simulate is None) == (envs is None):
+            raise ValueError("train_gan: give exactly one of simulate= (M host callables) and envs= (packed records)")
+        M, H = self.M, self.H
+        act = np.ones(M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(M)
+        if simulate is not None:
+            simulate = list(simulate)
+            if len(simulate) != M:
+                raise ValueError(f"simulate: {len(simulate)} callables for {M} cells")
+        scheds = np.asarray(scheds)
+        g = self.gan_graph(envs is not None)
+        hv, ov = g.hviews, g.oviews
+        hv["emb"][...] = np.asarray(emb, dtype=np.float32).reshape(M, 2 * H)
+        hv["sched"][...] = np.asarray(scheds, dtype=np.float32).reshape(M, H, H)
+        hv["active"][...] = act
+        res = [None] * M
+        if envs is not None:
+            rec = np.asarray(envs, dtype=np.float64).reshape(M, hv["envs"].shape[1])
+            hv["envs"][...] = np.where(act[:, None], rec, 0.0)
+            hv["tabD"][...], hv["tabG"][...] = self.sched.gan_tables(act)
+            g.upload("emb", "envs")
+            g.run(self, "E")
+            g.download(self, "ns", "sim")
+            scores = [(float(ov["sim"][c, 1]), float(ov["sim"][c, 3])) for c in range(M)]
+        else:
+            g.upload("emb", "active")
+            g.run(self, "A")
+            g.download(self, "ns", "probs")
+            scores = [None] * M
+            for c in np.flatnonzero(act):
+                ns_h = ov["ns"][c].astype(np.float64)
+                scores[c] = (simulate[c](ns_h), simulate[c](np.asarray(scheds[c], dtype=np.float64).reshape(H, H)))
+                hv["target"][c] = bce_target(*scores[c])
+            hv["tabD"][...], hv["tabG"][...] = self.sched.gan_tables(act)
+            g.upload("active", "tabG")
+            g.run(self, "B")
+            g.download(self, "probs_gen", "probs_after")
+        for c in np.flatnonzero(act):
+            new_score, orig_score = scores[c]
+            target = bce_target(new_score, orig_score)
+            self.gan_probs_after[c] = ov["probs_after"][c]
+            res[c] = (ov["ns"][c].astype(np.float64), new_score, orig_score, bce(ov["probs_gen"][c], [0.0, 1.0]),
+                      bce(ov["probs"][c], target))
+        return res
 
     # ---------------- the per-interval forward ----------------
     def detect(self, windows, scheds, active=None) -> dict:
@@ -1946,7 +2201,14 @@ class FleetTuner:
             spec = [("logits", f32, (M, H, 2)), ("protos", f32, (M, H, 2)), ("cls", i32, (M, H)), ("any", i32, (M,)),
                     ("probs", f32, (M, 2)), ("keep", i32, (M,)), ("final_target", i32, (M, H)),
                     ("gen_target", i32, (M, H))]
-            out = {name: torch.zeros(shp, dtype=dt, device=dev) for name, dt, shp in spec}
+            # one buffer, every part 8-byte aligned: detect_numpy downloads it with one copy
+            np_of = {f32: np.float32, i32: np.int32}
+            lay, total = _aligned_layout([(name, np_of[dt], shp) for name, dt, shp in spec])
+            buf = torch.zeros(total, dtype=torch.uint8, device=dev)
+            hbuf = torch.zeros(total, dtype=torch.uint8).pin_memory()
+            out = {name: buf[o:o + nb].view(_NP2TORCH[dt]).view(shp) for name, dt, shp, o, nb in lay}
+            self._detect_host = (buf, hbuf, {name: hbuf[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
+                                             for name, dt, shp, o, nb in lay})
             out["latent"] = None
             self._detect_io = (out, torch.ones(M, dtype=torch.int32, device=dev))
         out, act = self._detect_io
@@ -1962,11 +2224,20 @@ class FleetTuner:
             self._stream()), "pgp_forward1_many")
         return out
 
+    def detect_numpy(self, windows, scheds, active=None) -> dict:
+        """``detect`` and ONE download of all its outputs: numpy views of the
+        pinned copy (valid until the next call)."""
+        self.detect(windows, scheds, active)
+        buf, hbuf, views = self._detect_host
+        hbuf.copy_(buf, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return views
+
     # ---------------- one cell as a lone Trainer, and back ----------------
     def trainer(self, m: int):
         """Slot m as a lone ``Trainer`` + ``TuneState`` (weights, moments,
-        step counts, dropout seed, prototypes, factor): checkpoints and the
-        per-cell GAN step run through the single-cell code on it."""
+        step counts, dropout seed, prototypes, factor): checkpoints run
+        through the single-cell code on it."""
         tr = Trainer(self.H, self._template, lrs=self.lrs, device=self.device, max_batch=1, weight_decay=self.wd,
                      betas=(self.b1, self.b2), eps=self.eps, dropout=self.dropout, dropout_seed=self.seeds[m])
         tr.P.copy_(self.P[m])
