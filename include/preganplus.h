@@ -456,6 +456,27 @@ int pgp_tune_step1_many(int n_hosts, int n_protos, int n_cells, int n_steps, int
  * [n_cells][n_windows][H][2] fp64.  At most 65535 cells. */
 int pgp_tune_forward_cells(int n_hosts, int n_cells, int n_windows, const int* active, const float* windows,
                            const float* P, double* logits64, double* protos64, void* stream);
+/* accuracy()'s scores of every active cell (train.py:60-109: anomaly_accuracy,
+ * class_accuracy and accuracy's accumulation over the windows) from
+ * pgp_tune_forward_cells' outputs, in one launch, one workgroup per cell:
+ * logits64 / protos64 [n_cells][n_windows][H][2] fp64, y / cls
+ * [n_cells][n_windows][H] int32, state [n_cells][2K+3] fp64 (prototypes 0-2 are
+ * its first six doubles: the cell's prototypes after its last tuning step).
+ * Writes scores [n_cells][2] fp64 = {AScore, CScore} and flag [n_cells] int32.
+ * A host is correct when (logit 1 > logit 0) equals its label; a positive host
+ * is a hit when the MSE of its proto to its class's prototype (cls clipped to
+ * 0..2) is <= both others'; AScore is the mean over the windows of correct / H,
+ * CScore the mean over the windows with a positive label of hits / (1e-4 +
+ * positives).  fp64 in the reference's operation order without contraction:
+ * the bits train.accuracy_scores gives on the same arrays.  A cell without a
+ * positive label in any window — where the reference divides by zero
+ * (train.py:109) — gets flag 1 and its scores[.][1] is left unwritten;
+ * otherwise flag 0.  An inactive cell's scores and flag are left unwritten.
+ * Besides the errors above: PGP_ERR_ARG for n_protos < 3 or, with n_cells > 0,
+ * n_windows < 1. */
+int pgp_tune_scores_many(int n_hosts, int n_protos, int n_cells, int n_windows, const int* active,
+                         const double* logits64, const double* protos64, const int* y, const int* cls,
+                         const double* state, double* scores, int* flag, void* stream);
 /* pgp_forward1 per cell (run_model, PreGANPlus.py:115-136, of each
  * environment's own model): windows [n_cells][3][3H], sched [n_cells][H][H];
  * the prototypes are the first 2K doubles of the cell's state slot, the GAN

@@ -112,6 +112,7 @@ SIGNATURES = {
     "pgp_forward1": (i32, [i32, i32] + [vp] * 12 + [stream]),
     "pgp_tune_step1_many": (i32, [i32] * 5 + [vp] * 7 + [f64, f64] + [vp] * 3 + [f32, vp, stream]),
     "pgp_tune_forward_cells": (i32, [i32] * 3 + [vp] * 5 + [stream]),
+    "pgp_tune_scores_many": (i32, [i32] * 4 + [vp] * 8 + [stream]),
     "pgp_forward1_many": (i32, [i32] * 3 + [vp] * 13 + [stream]),
     "pgp_tune_dataset": (i32, [i32] * 3 + [vp] * 6 + [stream]),
     "pgp_tune_targets_dp_workspace_len": (sz, [i32]),

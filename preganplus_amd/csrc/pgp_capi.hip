@@ -15,6 +15,7 @@
 #include "pgp_tune.hpp"
 #include "pgp_tunef.hpp"
 #include "pgp_tunedp.hpp"
+#include "pgp_tunescore.hpp"
 
 // K2's default form (pgp_encoder_split); an A/B build sets 2
 #ifndef PGP_ENC_FORM
@@ -728,6 +729,22 @@ int pgp_tune_forward_cells(int n_hosts, int n_cells, int n_windows, const int* a
   if (!windows || !P || !logits || !protos) return fail(PGP_ERR_ARG, "bad tune_forward_cells arguments");
   HIPCHK(launch_fwd_cells(n_hosts, n_cells, n_windows, active, windows, P, logits, protos,
                           reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+// accuracy()'s scores per cell (train.py:60-109), after pgp_tune_forward_cells
+int pgp_tune_scores_many(int n_hosts, int n_protos, int n_cells, int n_windows, const int* active,
+                         const double* logits64, const double* protos64, const int* y, const int* cls,
+                         const double* state, double* scores, int* flag, void* stream) {
+  if (!tune1_supported(n_hosts)) return fail(PGP_ERR_UNSUPPORTED, "host count (scores for a fleet: 8 or 16)");
+  if (n_protos < 3) return fail(PGP_ERR_ARG, "class_accuracy needs prototypes 0-2");
+  if (n_cells < 0 || n_windows < 0) return fail(PGP_ERR_ARG, "n_cells >= 0, n_windows >= 0");
+  if (n_cells == 0) return PGP_OK;
+  if (n_windows < 1) return fail(PGP_ERR_ARG, "accuracy() needs at least one window");
+  if (!logits64 || !protos64 || !y || !cls || !state || !scores || !flag)
+    return fail(PGP_ERR_ARG, "bad tune_scores_many arguments");
+  HIPCHK(launch_tune_scores_cells(n_hosts, n_protos, n_cells, n_windows, active, logits64, protos64, y, cls, state,
+                                  scores, flag, reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;
 }
 

@@ -658,6 +658,34 @@ class _RecoverIO:
         return o[0, 0].copy(), o[1, 0].copy()
 
 
+class _RecoverManyIO:
+    """``_RecoverIO`` for M rows: keep [M] | final_target [M,C] | cur_host [M,C]
+    in one upload, one K5 launch at batch M, moves | hosts_from [2,M,C] in one
+    download, one synchronisation."""
+
+    def __init__(self, M, C, device):
+        self.M, self.C = M, C
+        n = M * (1 + 2 * C)
+        self.hin = torch.zeros(n, dtype=torch.int32).pin_memory()
+        self.din = torch.zeros(n, dtype=torch.int32, device=device)
+        self.dout = torch.zeros((2, M, C), dtype=torch.int32, device=device)
+        self.hout = torch.zeros((2, M, C), dtype=torch.int32).pin_memory()
+        h = self.hin.numpy()
+        self.keep, self.final_target, self.cur = h[:M], h[M:M + M * C].reshape(M, C), h[M + M * C:].reshape(M, C)
+
+    def run(self):
+        """K5 on the staged rows (``keep`` / ``final_target`` / ``cur``, filled by the caller) ->
+        (moves [M,C], hosts_from [M,C]), views of the pinned download."""
+        M, C = self.M, self.C
+        self.din.copy_(self.hin, non_blocking=True)
+        migrations(self.din[:M], self.din[M:M + M * C].view(M, C), self.din[M + M * C:].view(M, C),
+                   out=(self.dout[0], self.dout[1]))
+        self.hout.copy_(self.dout, non_blocking=True)
+        torch.cuda.current_stream(self.din.device).synchronize()
+        o = self.hout.numpy()
+        return o[0], o[1]
+
+
 def _recover(env, hosts, schedule_data, original_decision, keep_original, device, final_target=None, io=None):
     """recover_decision's decision loop (PreGAN.py:77-95 == PreGANPlus.py:84-105)
     on the device (K5, pgp_migrations): every placed container moves to the first
@@ -892,9 +920,16 @@ class PreGANPlusFleetRecovery:
     ``save_checkpoints(folder, m)`` writes cell m's three checkpoints through
     ``FleetTuner.trainer(m)``.  The lone plugin's per-call asynchronous
     ``save_gan`` writer is out of scope here and off: nothing is written
-    unless ``save_checkpoints`` is called."""
+    unless ``save_checkpoints`` is called.
 
-    def __init__(self, hosts, weights, extras, training=False, dropout=0.0, dropout_seeds=None, device=None, env=""):
+    ``device_finish=True`` computes the same with less per-cell host work: the
+    tuning graphs score every cell on the device (``tune(score="device")``,
+    ``pgp_tune_scores_many``), and the cells' decisions are recovered in one
+    K5 call at batch M (one upload, launch, download and synchronisation)
+    instead of one per cell."""
+
+    def __init__(self, hosts, weights, extras, training=False, dropout=0.0, dropout_seeds=None, device=None, env="",
+                 device_finish=False):
         if hosts not in TR.FUSED_STEP_HOSTS:
             raise ValueError(f"the fleet plugin runs the fused batch-1 steps: hosts in {TR.FUSED_STEP_HOSTS}, "
                              f"not {hosts}")
@@ -926,6 +961,8 @@ class PreGANPlusFleetRecovery:
         self.envs = None
         self._tune_stream = None
         self._rio = None
+        self.device_finish = bool(device_finish)
+        self._rio_many = None
 
     def setEnvironments(self, envs):
         envs = list(envs)
@@ -992,7 +1029,8 @@ class PreGANPlusFleetRecovery:
                     w[m], y[m], c[m] = data[m][0], np.asarray(data[m][2]).reshape(n, H), \
                         np.asarray(data[m][3]).reshape(n, H)
                     on[m] = True
-                pending.append((ms, ft.tune_launch(w, y, c, on, score=True, stream=self._tune_stream)))
+                pending.append((ms, ft.tune_launch(w, y, c, on, score="device" if self.device_finish else True,
+                                                   stream=self._tune_stream)))
             gan = ft.train_gan(emb, scheds, simulate=[self._score(m) for m in range(M)], active=act)
             for m in cells:                  # PreGANPlus.py:76-77
                 self.epoch[m] += 1
@@ -1013,6 +1051,9 @@ class PreGANPlusFleetRecovery:
                 loss = float(np.mean([a for a, _ in losses]) + np.mean([t for _, t in losses]))   # train.py:56-57
                 factor = ft.states[m].factor + TR.PROTO_UPDATE_MIN
                 self.accuracy_list[m].append((loss, factor, scores[0], scores[1]))                # :58
+        if self.device_finish:
+            self._recover_many(cells, res, original_decisions, out["final_target"])
+            return res
         if self._rio is None:
             self._rio = _RecoverIO(H, self.device)
         for m in cells:                      # PreGANPlus.py:83-105, each cell on its own updated gate
@@ -1024,6 +1065,38 @@ class PreGANPlusFleetRecovery:
             if hf is not None:
                 self.hosts_from[m] = hf
         return res
+
+    def _recover_many(self, cells, res, original_decisions, final_target):
+        """``_recover`` (PreGANPlus.py:83-105) for every deciding cell in one K5 call at batch M, each on
+        its own updated gate: fills ``res`` and ``hosts_from`` as the per-cell loop does.  Cells that are
+        inactive or hold a ZeroDivisionError are staged as keep = 1; their rows are ignored."""
+        M, H = self.M, self.hosts
+        if self._rio_many is None:
+            self._rio_many = _RecoverManyIO(M, H, self.device)
+        io = self._rio_many
+        io.keep[:] = 1
+        io.cur[:] = -1
+        io.final_target[...] = final_target
+        deciding = []
+        for m in cells:
+            if isinstance(res[m], ZeroDivisionError):
+                continue
+            p = self.tuner.gan_probs_after[m]
+            if p[0] > p[1]:                  # the original decision stands (PreGANPlus.py:85-86)
+                res[m] = original_decisions[m]
+                continue
+            io.keep[m] = 0
+            cur = io.cur[m]
+            for c in self.envs[m].containerlist:
+                if c and c.getHostID() != -1:
+                    cur[c.id] = c.getHostID()
+            deciding.append(m)
+        if not deciding:
+            return
+        moves, hosts_from = io.run()
+        for m in deciding:
+            res[m] = assemble_decision(original_decisions[m], moves[m], io.cur[m])
+            self.hosts_from[m] = hosts_from[m].tolist()
 
     # -- utils.py:49-58 per cell: the explicit full save of PreGANPlusRecovery.save_checkpoints --
     def save_checkpoints(self, folder, m):

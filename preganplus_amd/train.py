@@ -1271,6 +1271,57 @@ def accuracy_scores(lg, pr, anom, cls, P):
     return anomaly_correct / n, class_correct / class_total
 
 
+def _zero_division_args():
+    """The args of the ZeroDivisionError ``accuracy_scores`` ends on: with class_total = 0 its
+    class_correct is still the int 0, so this interpreter's message for int / int."""
+    try:
+        0 / 0
+    except ZeroDivisionError as e:
+        return e.args
+
+
+_ZERO_DIVISION_ARGS = _zero_division_args()
+
+
+def accuracy_scores_many(lg, pr, anom, cls, P):
+    """``accuracy_scores`` over a leading cell axis, without raising: lg / pr
+    [M,n,H,2] fp64, anom / cls [M,n,H], P [M,K,2] (K >= 3) -> (scores [M,2]
+    fp64 = (AScore, CScore) per cell, flag [M] int32).  flag[m] = 1 where
+    ``accuracy_scores`` raises ZeroDivisionError on cell m's arrays (no window
+    with a positive label); that cell's CScore is NaN.  Every other value has
+    the bits ``accuracy_scores`` returns.  The host statement of
+    ``pgp_tune_scores_many``'s layout and arithmetic (pgp_tunescore.hip)."""
+    lg, pr = np.asarray(lg, dtype=np.float64), np.asarray(pr, dtype=np.float64)
+    M, n, H = lg.shape[0], lg.shape[1], lg.shape[2]
+    anom = np.asarray(anom).reshape(M, n, H)
+    cls = np.asarray(cls).reshape(M, n, H).astype(np.int64)
+    P = np.asarray(P, dtype=np.float64)[:, :3, :]
+    res = (lg[..., 1] > lg[..., 0]).astype(np.int64)
+    correct = np.sum(res == anom, axis=2)                                         # [M,n]
+    dist = np.mean((pr[:, :, :, None, :] - P[:, None, None, :, :]) ** 2, axis=-1)   # [M,n,H,3]
+    c = np.clip(cls, 0, 2)
+    pos = np.take_along_axis(dist, c[..., None], axis=-1)[..., 0]
+    n0 = np.where(c == 0, dist[..., 1], dist[..., 0])
+    n1 = np.where(c == 2, dist[..., 1], dist[..., 2])
+    hits = np.sum((anom > 0) & (pos <= n0) & (pos <= n1), axis=2)
+    npos = np.sum(anom > 0, axis=2)
+    has = np.sum(anom, axis=2) > 0
+    anomaly_correct, class_correct, class_total = np.zeros(M), np.zeros(M), np.zeros(M)
+    for i in range(n):                                    # the windows in order, every cell at once
+        anomaly_correct += correct[:, i] / float(H)
+        total = np.full(M, 1e-4)
+        for k in range(H):                                # total += 1 once per positive
+            total = np.where(k < npos[:, i], total + 1.0, total)
+        class_correct += np.where(has[:, i], hits[:, i] / total, 0.0)
+        class_total += has[:, i]
+    flag = (class_total == 0).astype(np.int32)
+    scores = np.empty((M, 2), dtype=np.float64)
+    scores[:, 0] = anomaly_correct / n
+    scores[:, 1] = np.nan
+    np.divide(class_correct, class_total, out=scores[:, 1], where=class_total > 0)
+    return scores, flag
+
+
 def dp_groups():
     """Process groups of the data-parallel C3 step: (tuning group,
     GAN group).  At world size > 1 the GAN step's gradient all-reduces get a
@@ -1767,11 +1818,15 @@ class _FleetGraph:
     whatever the fleet's size — and the copy of the state into the output
     gather.  Inputs in one staging buffer (``fleet_staging_layout``), outputs
     in one fp64 buffer: loss [M,n,2] | state [M,2K+3] | logits [M,n,H,2] |
-    protos [M,n,H,2]."""
+    protos [M,n,H,2].  ``score="device"`` adds one ``pgp_tune_scores_many``
+    launch behind the forward; its buffer is loss | state | scores [M,2] |
+    flags [M] int32 | logits | protos, of which the first ``n_down`` doubles
+    (up to the flags, every part 8-byte aligned) are downloaded."""
 
-    def __init__(self, ft: "FleetTuner", n: int, score: bool):
+    def __init__(self, ft: "FleetTuner", n: int, score):
         H, M, K, dev = ft.H, ft.M, ft.K, ft.device
         self.n, self.score = n, score
+        self.device_score = score == "device"
         lay, total = fleet_staging_layout(H, M, n, K, len(ft.sel))
         self.din = torch.zeros(total, dtype=torch.uint8, device=dev)
         self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
@@ -1781,11 +1836,20 @@ class _FleetGraph:
             self.hviews[name] = self.hin[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
         S = 2 * K + 3
         self.o_state = 2 * n * M
-        self.o_lg = self.o_state + M * S
+        if self.device_score:
+            # loss | state | scores [M,2] | flags [M] int32 (padded to whole doubles) come down; the
+            # forward's logits / protos behind them stay on the device (pgp_tune_scores_many reads them)
+            self.o_scores = self.o_state + M * S
+            self.o_flag = self.o_scores + 2 * M
+            self.o_lg = self.n_down = self.o_flag + (M + 1) // 2
+        else:
+            self.o_lg = self.o_state + M * S
+            self.n_down = self.o_lg + (4 * n * H * M if score else 0)
         self.o_pr = self.o_lg + 2 * n * H * M
         nout = self.o_lg + (4 * n * H * M if score else 0)
         self.dout = torch.zeros(nout, dtype=torch.float64, device=dev)
-        self.hout = torch.zeros(nout, dtype=torch.float64).pin_memory()
+        self.hout = torch.zeros(self.n_down, dtype=torch.float64).pin_memory()
+        self.down = self.dout[:self.n_down]
         self.loss = self.dout[:self.o_state]
         self.graph = None
 
@@ -1794,9 +1858,11 @@ class _FleetGraph:
         for i in range(self.n):
             ft.step_many(self, i)
             ft.adamw_many(self, i)
-        self.dout[self.o_state:self.o_lg].copy_(self.state.view(-1))
+        self.dout[self.o_state:self.o_state + self.state.numel()].copy_(self.state.view(-1))
         if self.score:
             ft.forward_cells(self)
+        if self.device_score:
+            ft.scores_many(self)
 
     def capture(self, ft: "FleetTuner"):
         self.graph = torch.cuda.CUDAGraph()
@@ -1990,13 +2056,25 @@ class FleetTuner:
             self.H, self.M, g.n, g.active.data_ptr(), g.W.data_ptr(), self.P.data_ptr(),
             g.dout[g.o_lg:].data_ptr(), g.dout[g.o_pr:].data_ptr(), self._stream()), "pgp_tune_forward_cells")
 
-    def graph(self, n: int, score: bool = True, capture: bool = True) -> _FleetGraph:
-        """The call's buffers and captured graph, cached per (n, score); the
-        fleet's size, prototype count and dropout are fixed per tuner."""
-        key = (self.M, int(n), self.K, bool(score), self.dropout)
+    def scores_many(self, g: _FleetGraph):
+        """accuracy()'s scores of every active cell from the forward's device output and the
+        cells' updated prototypes (``pgp_tune_scores_many``)."""
+        _native.check(self._L.pgp_tune_scores_many(
+            self.H, self.K, self.M, g.n, g.active.data_ptr(), g.dout[g.o_lg:].data_ptr(),
+            g.dout[g.o_pr:].data_ptr(), g.Y.data_ptr(), g.C.data_ptr(), g.state.data_ptr(),
+            g.dout[g.o_scores:].data_ptr(), g.dout[g.o_flag:].data_ptr(), self._stream()), "pgp_tune_scores_many")
+
+    def graph(self, n: int, score=True, capture: bool = True) -> _FleetGraph:
+        """The call's buffers and captured graph, cached per (n, score mode:
+        False, True or "device"); the fleet's size, prototype count and
+        dropout are fixed per tuner."""
+        if isinstance(score, str) and score != "device":
+            raise ValueError(f'score: True, False or "device", not {score!r}')
+        mode = "device" if score == "device" else bool(score)
+        key = (self.M, int(n), self.K, mode, self.dropout)
         g = self._graphs.get(key)
         if g is None:
-            g = self._graphs[key] = _FleetGraph(self, int(n), bool(score))
+            g = self._graphs[key] = _FleetGraph(self, int(n), mode)
         if capture and g.graph is None:
             g.capture(self)
         return g
@@ -2031,32 +2109,50 @@ class FleetTuner:
 
     def results(self, g: _FleetGraph, out, anom, cls, act):
         """Per cell what ``backprop`` returns from the downloaded gather; updates the active cells' host state."""
-        M, n, H, S = self.M, g.n, self.H, 2 * self.K + 3
+        M, n, H, K, S = self.M, g.n, self.H, self.K, 2 * self.K + 3
         self.state_dev = g.state
-        loss = out[:g.o_state].reshape(M, n, 2)
-        state = out[g.o_state:g.o_lg].reshape(M, S)
+        state = out[g.o_state:g.o_state + M * S].reshape(M, S)
+        losses = out[:g.o_state].reshape(M, n, 2).tolist()      # one conversion for the fleet
+        tail = state[:, 2 * K:].tolist()
         res = [None] * M
-        for c in np.flatnonzero(act):
-            self.states[c].from_vector(state[c])
-            losses = [tuple(r) for r in loss[c].tolist()]
+        device = g.score == "device"
+        if device:
+            sc = out[g.o_scores:g.o_flag].reshape(M, 2).tolist()
+            flag = out[g.o_flag:g.n_down].view(np.int32)[:M].tolist()
+        elif g.score:
+            lgs, prs = out[g.o_lg:g.o_pr].reshape(M, n, H, 2), out[g.o_pr:].reshape(M, n, H, 2)
+        for c in np.flatnonzero(act).tolist():
+            st = self.states[c]                                 # TuneState.from_vector(state[c])
+            st.protos = np.array(state[c, :2 * K], dtype=np.float64).reshape(K, 2)
+            st.factor, st.num_zero, st.num_ones = tail[c][0], int(tail[c][1]), int(tail[c][2])
+            ls = [tuple(r) for r in losses[c]]
             if not g.score:
-                res[c] = losses
+                res[c] = ls
                 continue
-            lg = out[g.o_lg:g.o_pr].reshape(M, n, H, 2)[c]
-            pr = out[g.o_pr:].reshape(M, n, H, 2)[c]
             self.tune_errors.pop(c, None)
+            if device:
+                if flag[c]:
+                    # the kernel met class_total == 0 (train.py:109): the exception accuracy_scores raises on
+                    # these inputs (class_correct / class_total, both still the int 0), built here and so
+                    # without a traceback — as below, one whose frames name this tuner would tie it into a
+                    # reference cycle
+                    scores, self.tune_errors[c] = None, ZeroDivisionError(*_ZERO_DIVISION_ARGS)
+                else:
+                    scores = (sc[c][0], sc[c][1])
+                res[c] = (ls, scores)
+                continue
             try:
-                scores = accuracy_scores(lg, pr, anom[c], cls[c], self.states[c].protos)
+                scores = accuracy_scores(lgs[c], prs[c], anom[c], cls[c], st.protos)
             except ZeroDivisionError as e:   # no window of the cell has a positive label: the lone call raises here
                 scores = None                # (train.py:109); one such cell must not stop the fleet
                 # the exception the lone call raises, for a caller that hands it on; without its traceback,
                 # whose frame names this tuner: kept, it would tie the tuner into a reference cycle and leave
                 # its graphs and pinned buffers to the cyclic collector, which may run inside a later capture
                 self.tune_errors[c] = e.with_traceback(None)
-            res[c] = (losses, scores)
+            res[c] = (ls, scores)
         return res
 
-    def tune(self, wins, anom, cls, active=None, score: bool = True):
+    def tune(self, wins, anom, cls, active=None, score=True):
         """One interval's tuning of every active cell: wins [M,n,3,3H], anom /
         cls [M,n,H], active [M] (None: all).  Returns a list of M entries: for
         an active cell what ``backprop(tr_m, st_m, wins[m], anom[m], cls[m],
@@ -2064,10 +2160,13 @@ class FleetTuner:
         call raises ZeroDivisionError: a cell without a positive label in any
         window), None for the others, whose slots and counts stay untouched.
         One upload from pinned staging (``active`` among the inputs: one graph
-        serves any subset), one graph replay, one download."""
+        serves any subset), one graph replay, one download.
+        ``score="device"`` returns the same, with the scores computed inside the
+        graph (``pgp_tune_scores_many``) instead of per cell on the host: the
+        download is loss | state | scores | flags, the logits stay on the device."""
         return self.tune_launch(wins, anom, cls, active, score)()
 
-    def tune_launch(self, wins, anom, cls, active=None, score: bool = True, stream=None):
+    def tune_launch(self, wins, anom, cls, active=None, score=True, stream=None):
         """``tune`` up to its device work, launched on ``stream`` (default: the
         current one); returns the function that waits for it and returns what
         ``tune`` would (``backprop``'s ``defer``, for a fleet: the fleet plugin
@@ -2085,7 +2184,7 @@ class FleetTuner:
         with torch.cuda.stream(st):
             g.din.copy_(g.hin, non_blocking=True)
             g.graph.replay()
-            g.hout.copy_(g.dout, non_blocking=True)
+            g.hout.copy_(g.down, non_blocking=True)
 
         def finish():
             st.synchronize()
