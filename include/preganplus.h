@@ -499,6 +499,23 @@ int pgp_forward1_many(int n_hosts, int n_protos, int n_cells, const int* active,
  * rows (PreGANPlus.py:107-112: [R-3, R-3, R-2]) infer [E,3,3H]. */
 int pgp_tune_dataset(int n_hosts, int n_env, int n_rows, const double* series, const double* train_max,
                      float* windows, int* y, int* cls, float* infer, void* stream);
+/* pgp_tune_dataset for a fleet of n_cells cells, each on its own training
+ * series (load_on_the_fly_dataset, utils.py:40-47, normalised by utils.py:94-95
+ * with the CELL's np.max(train_time_data, axis=0); run_encoder's window,
+ * PreGANPlus.py:107-112): series [n_cells][n_rows][3H] fp64, train_max
+ * [n_cells][3H] fp64; writes windows [n_cells][n_rows][3][3H] fp32, y / cls
+ * [n_cells][n_rows][H] int32 and, where not NULL, positive [n_cells][n_rows]
+ * int32 (1 where a host of the window has y == 1) and infer [n_cells][3][3H].
+ * Every value has the bits pgp_tune_dataset gives for that cell alone with its
+ * train_max.  active [n_cells] int32 or NULL (all): a cell with active == 0 is
+ * skipped, its inputs are not read and its output rows are left unwritten.
+ * One launch.  Checked before anything is enqueued: PGP_ERR_UNSUPPORTED for
+ * n_hosts outside 1..64; PGP_ERR_ARG for n_cells < 0, n_rows outside 1..16 or,
+ * with n_cells > 0, a NULL series, train_max, windows, y or cls.  n_cells == 0
+ * is PGP_OK and launches nothing. */
+int pgp_tune_dataset_cells(int n_hosts, int n_cells, int n_rows, const int* active, const double* series,
+                           const double* train_max, float* windows, int* y, int* cls, int* positive, float* infer,
+                           void* stream);
 /* doubles of workspace pgp_tune_targets_dp needs for a batch (zero-filled
  * once before first use: slot 0 is the finishing counter, left at zero) */
 size_t pgp_tune_targets_dp_workspace_len(int batch);

@@ -115,6 +115,7 @@ SIGNATURES = {
     "pgp_tune_scores_many": (i32, [i32] * 4 + [vp] * 8 + [stream]),
     "pgp_forward1_many": (i32, [i32] * 3 + [vp] * 13 + [stream]),
     "pgp_tune_dataset": (i32, [i32] * 3 + [vp] * 6 + [stream]),
+    "pgp_tune_dataset_cells": (i32, [i32] * 3 + [vp] * 8 + [stream]),
     "pgp_tune_targets_dp_workspace_len": (sz, [i32]),
     "pgp_tune_targets_dp": (i32, [i32] * 3 + [vp] * 5 + [f64] + [vp] * 5 + [stream]),
     "pgp_tune_state_apply": (i32, [i32, vp, vp, f64, i32, pi32, vp, vp, f64, f64, f64, stream]),

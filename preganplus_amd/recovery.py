@@ -926,10 +926,19 @@ class PreGANPlusFleetRecovery:
     tuning graphs score every cell on the device (``tune(score="device")``,
     ``pgp_tune_scores_many``), and the cells' decisions are recovered in one
     K5 call at batch M (one upload, launch, download and synchronisation)
-    instead of one per cell."""
+    instead of one per cell.
+
+    ``device_dataset=True`` computes the same with the cells' datasets built on
+    the device: per cell the host only copies the last ``min(len, 10)`` rows
+    of its series into the pinned staging of its length group; one
+    ``FleetTuner.dataset`` call per distinct length writes the tuning windows
+    and labels where the tuning graph reads them and every cell's inference
+    window where ``detect`` reads it; the labels come down with the detect
+    download, and ``tune_launch(inputs="device")`` uploads only the staging
+    behind the windows and labels.  Both flags combine freely."""
 
     def __init__(self, hosts, weights, extras, training=False, dropout=0.0, dropout_seeds=None, device=None, env="",
-                 device_finish=False):
+                 device_finish=False, device_dataset=False):
         if hosts not in TR.FUSED_STEP_HOSTS:
             raise ValueError(f"the fleet plugin runs the fused batch-1 steps: hosts in {TR.FUSED_STEP_HOSTS}, "
                              f"not {hosts}")
@@ -963,6 +972,10 @@ class PreGANPlusFleetRecovery:
         self._rio = None
         self.device_finish = bool(device_finish)
         self._rio_many = None
+        self.device_dataset = bool(device_dataset)
+        # each cell's np.max(train_time_data, axis=0) (utils.py:94-95), once: the device dataset's divisors
+        self.train_max = (np.stack([np.max(t, axis=0) for t in self.train_time_data]).astype(np.float64)
+                          if self.device_dataset else None)
 
     def setEnvironments(self, envs):
         envs = list(envs)
@@ -981,6 +994,26 @@ class PreGANPlusFleetRecovery:
             td = td[-3:]
         return TR.convert_to_windows(td)[-1]
 
+    def _device_datasets(self, score):
+        """Every cell's dataset and inference window on the device: per cell its row count
+        n = min(len(time_series), LATEST_WINDOW_SIZE) and a copy of its last n rows into the pinned
+        staging of its length group, then one ``FleetTuner.dataset`` call per distinct n (active = the
+        group).  Returns {n: the call's buffers}; ``self._rows[m]`` is cell m's n.  Nothing is waited for."""
+        ft, M = self.tuner, self.M
+        groups = {}
+        self._rows = rows = [0] * M
+        for m, e in enumerate(self.envs):
+            ts = e.stats.time_series
+            n = rows[m] = min(len(ts), TR.LATEST_WINDOW_SIZE)
+            if n == 0:
+                raise ValueError(f"cell {m}: an empty time series has no inference window")
+            io = groups.get(n)
+            if io is None:
+                io = groups[n] = (ft.dataset_io(n, score), np.zeros(M, dtype=bool))
+            io[0].series[m] = ts[-n:]
+            io[1][m] = True
+        return {n: ft.dataset(n, None, self.train_max, on, score) for n, (_, on) in groups.items()}
+
     def _score(self, m):
         def score(schedule):      # utils.py:97-100
             e, r = self.envs[m].stats.runSimulation(torch.tensor(schedule))
@@ -993,7 +1026,12 @@ class PreGANPlusFleetRecovery:
         if self.envs is None or len(original_decisions) != M:
             raise ValueError(f"run_model: setEnvironments first, and one original decision per cell ({M})")
         scheds = np.stack([np.asarray(e.scheduler.result_cache, dtype=np.float64) for e in self.envs])
-        wins = np.stack([self._input_window(m) for m in range(M)])
+        score = "device" if self.device_finish else True
+        if self.device_dataset:
+            datasets = self._device_datasets(score)
+            wins = ft.infer_windows
+        else:
+            wins = np.stack([self._input_window(m) for m in range(M)])
         out = ft.detect_numpy(wins, scheds)
         act = out["any"].astype(bool).copy()
         res = list(original_decisions)       # no anomaly: the original decision (PreGANPlus.py:119-127)
@@ -1009,11 +1047,15 @@ class PreGANPlusFleetRecovery:
         # the tuning graphs first, on their own stream (they share no data with the GAN step), one
         # tune() per distinct dataset length; then train_gan around the host simulators; the tuning's
         # host bookkeeping and accuracy_list entry after train_gan's, in the reference's order
-        data = {m: TR.on_the_fly_dataset(self.envs[m].stats.time_series, self.envs[m].stats.schedule_series,
-                                         self.train_time_data[m]) for m in cells}
         groups = {}
-        for m in cells:
-            groups.setdefault(np.asarray(data[m][0]).shape[0], []).append(m)
+        if self.device_dataset:
+            for m in cells:
+                groups.setdefault(self._rows[m], []).append(m)
+        else:
+            data = {m: TR.on_the_fly_dataset(self.envs[m].stats.time_series, self.envs[m].stats.schedule_series,
+                                             self.train_time_data[m]) for m in cells}
+            for m in cells:
+                groups.setdefault(np.asarray(data[m][0]).shape[0], []).append(m)
         cur = torch.cuda.current_stream(self.device)
         if self._tune_stream is None:
             self._tune_stream = torch.cuda.Stream(self.device)
@@ -1021,6 +1063,13 @@ class PreGANPlusFleetRecovery:
         pending = []
         try:
             for n, ms in groups.items():
+                if self.device_dataset:      # W / Y / C are on the device; the labels came down with detect's outputs
+                    on = np.zeros(M, dtype=bool)
+                    on[ms] = True
+                    d = datasets[n]
+                    pending.append((ms, ft.tune_launch(None, None, None, on, score=score, stream=self._tune_stream,
+                                                       inputs="device", labels=(d.y, d.cls, d.positive))))
+                    continue
                 w = np.zeros((M, n, 3, 3 * H), dtype=np.float32)
                 y = np.zeros((M, n, H), dtype=np.int32)
                 c = np.zeros((M, n, H), dtype=np.int32)
@@ -1029,8 +1078,7 @@ class PreGANPlusFleetRecovery:
                     w[m], y[m], c[m] = data[m][0], np.asarray(data[m][2]).reshape(n, H), \
                         np.asarray(data[m][3]).reshape(n, H)
                     on[m] = True
-                pending.append((ms, ft.tune_launch(w, y, c, on, score="device" if self.device_finish else True,
-                                                   stream=self._tune_stream)))
+                pending.append((ms, ft.tune_launch(w, y, c, on, score=score, stream=self._tune_stream)))
             gan = ft.train_gan(emb, scheds, simulate=[self._score(m) for m in range(M)], active=act)
             for m in cells:                  # PreGANPlus.py:76-77
                 self.epoch[m] += 1

@@ -908,6 +908,36 @@ def on_the_fly_dataset(time_series, schedule_series, train_time_data):
     return convert_to_windows(td), sched, anom, cls
 
 
+def on_the_fly_dataset_many(series, train_max):
+    """``on_the_fly_dataset`` plus run_encoder's window (PreGANPlus.py:107-112)
+    over a leading cell axis, the host statement of ``pgp_tune_dataset_cells``:
+    series [M,n,3H] (each cell's last n rows of stats.time_series), train_max
+    [M,3H] (each cell's np.max(train_time_data, axis=0)) -> windows [M,n,3,3H]
+    fp32, y / cls [M,n,H] int32, positive [M,n] int32 (a host of the window has
+    y == 1), infer [M,3,3H] fp32.  Per value the operations of
+    ``normalize_test_time_data`` / ``form_test_dataset`` / ``convert_to_windows``
+    in their order: the same bits as a loop over the cells."""
+    series = np.asarray(series, dtype=np.float64)
+    M, n, F = series.shape
+    td = series / (np.asarray(train_max, dtype=np.float64).reshape(M, 1, F) + 1e-8)
+    vi = (n - 1) * (PERCENTILES / 100.0)          # percentile_linear, along the rows of every cell
+    lo = np.floor(vi)
+    gm = vi - lo
+    ilo = int(lo)
+    ihi = min(ilo + 1, n - 1)
+    srt = np.sort(td, axis=1)
+    a, b = srt[:, ilo], srt[:, ihi]
+    d = b - a
+    thr = b - d * (1.0 - gm) if gm >= 0.5 else a + d * gm
+    y = (td > thr[:, None, :]).reshape(M, n, F // 3, 3).any(axis=3)
+    cls = np.argmax(td.reshape(M, n, F // 3, 3), axis=3)
+    i = np.arange(n)[:, None] - 3 + np.arange(3)[None, :]
+    wins = td[:, np.maximum(i, 0)]
+    rows = [n - 3, n - 3, n - 2] if n >= 3 else [0, 0, 0]
+    return (wins.astype(np.float32), y.astype(np.int32), cls.astype(np.int32), y.any(axis=2).astype(np.int32),
+            td[:, rows].astype(np.float32))
+
+
 FUSED_STEP_HOSTS = (8, 16)   # pgp_tune_step1's compiled host counts
 
 
@@ -1831,6 +1861,8 @@ class _FleetGraph:
         self.din = torch.zeros(total, dtype=torch.uint8, device=dev)
         self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
         self.hviews = {}
+        self.span = {name: (o, o + nb) for name, _, _, o, nb in lay}   # byte ranges of the staging's parts
+        self.data = None            # the device-written dataset's buffers (FleetTuner.dataset), made on first use
         for name, dt, shp, o, nb in lay:
             setattr(self, name, self.din[o:o + nb].view(_NP2TORCH[dt]).view(shp))
             self.hviews[name] = self.hin[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
@@ -1869,6 +1901,35 @@ class _FleetGraph:
         torch.cuda.synchronize(ft.device)
         with torch.cuda.graph(self.graph):
             self.issue(ft)
+
+
+class _FleetData:
+    """The buffers of one ``FleetTuner.dataset`` call on a ``_FleetGraph``:
+    the pinned and device staging series [M,n,3H] fp64 | active [M] int32
+    (one upload), the device ``positive`` [M,n] int32, and the pinned copy of
+    the graph's Y | C span and of ``positive`` that the labels come down
+    into (``y`` / ``cls`` / ``positive``: numpy views of it, valid once the
+    stream the call ran on has been synchronised, until the next call)."""
+
+    def __init__(self, ft: "FleetTuner", g: _FleetGraph):
+        H, M, n, dev = ft.H, ft.M, g.n, ft.device
+        lay, total = _aligned_layout([("series", np.float64, (M, n, 3 * H)), ("active", np.int32, (M,))])
+        self.din = torch.zeros(total, dtype=torch.uint8, device=dev)
+        self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self.hviews = {}
+        for name, dt, shp, o, nb in lay:
+            setattr(self, "d_" + name, self.din[o:o + nb].view(_NP2TORCH[dt]).view(shp))
+            self.hviews[name] = self.hin[o:o + nb].view(_NP2TORCH[dt]).view(shp).numpy()
+        self.series = self.hviews["series"]                 # the caller fills the rows of its cells here
+        self.d_positive = torch.zeros((M, n), dtype=torch.int32, device=dev)
+        (y0, y1), (c0, c1) = g.span["Y"], g.span["C"]
+        self.labels = g.din[y0:c1]                          # Y | C, one copy
+        self.hlabels = torch.zeros(c1 - y0, dtype=torch.uint8).pin_memory()
+        self.hpositive = torch.zeros((M, n), dtype=torch.int32).pin_memory()
+        self.y = self.hlabels[:y1 - y0].view(torch.int32).view(M, n, H).numpy()
+        self.cls = self.hlabels[c0 - y0:].view(torch.int32).view(M, n, H).numpy()
+        self.positive = self.hpositive.numpy()
+        self.upload_bytes = total
 
 
 class _FleetGanGraph:
@@ -2026,6 +2087,10 @@ class FleetTuner:
         self._gan_graphs = {}
         self.gan_capture = True     # False: train_gan issues its launches eagerly (the tests hold both equal)
         self.gan_probs_after = np.zeros((M, 2), dtype=np.float32)
+        # the device-written datasets (dataset): the cells' training maxima [M,3H] fp64 on the device, uploaded
+        # once, and the fleet-wide inference windows [M,3,3H] (detect's input), both made on first use
+        self._train_max = self._train_max_src = None
+        self.infer_windows = None
 
     def _stream(self):
         idx = self.device.index
@@ -2079,13 +2144,18 @@ class FleetTuner:
             g.capture(self)
         return g
 
-    def stage(self, g: _FleetGraph, wins, anom, cls, active=None):
+    def stage(self, g: _FleetGraph, wins, anom, cls, active=None, device_inputs: bool = False, positive=None):
         """Fill the graph's pinned staging from the call's inputs and the
         host bookkeeping (resetting num_zero / num_ones, taking each cell's
         dropout base before its counts advance, building its AdamW table).
-        Returns the checked (anom, cls, active)."""
+        Returns the checked (anom, cls, active).  ``device_inputs``: W / Y / C
+        are on the device already (``dataset``); ``wins`` is not read, anom /
+        cls are the downloaded labels (positive [M,n], if given, the kernel's
+        "a host of the window has y == 1" beside them), and only the parts
+        from ``sched`` on are staged."""
         M, n, H = self.M, g.n, self.H
-        wins = np.asarray(wins, dtype=np.float32).reshape(M, n, 3, 3 * H)
+        if not device_inputs:
+            wins = np.asarray(wins, dtype=np.float32).reshape(M, n, 3, 3 * H)
         anom = np.asarray(anom).reshape(M, n, H)
         cls = np.asarray(cls).reshape(M, n, H)
         act = np.ones(M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(M)
@@ -2095,11 +2165,12 @@ class FleetTuner:
         for c in np.flatnonzero(act):
             self.states[c].num_zero, self.states[c].num_ones = 1, 1
         bases = self.sched.drop_bases()
-        tab = self.sched.tables(np.any(anom > 0, axis=2), act)
+        tab = self.sched.tables(np.any(anom > 0, axis=2) if positive is None else positive, act)
         hv = g.hviews
-        hv["W"][...] = wins
-        hv["Y"][...] = anom
-        hv["C"][...] = cls
+        if not device_inputs:
+            hv["W"][...] = wins
+            hv["Y"][...] = anom
+            hv["C"][...] = cls
         hv["sched"][...] = tab
         hv["active"][...] = act
         hv["state"][...] = np.stack([s.vector() for s in self.states])
@@ -2166,23 +2237,43 @@ class FleetTuner:
         download is loss | state | scores | flags, the logits stay on the device."""
         return self.tune_launch(wins, anom, cls, active, score)()
 
-    def tune_launch(self, wins, anom, cls, active=None, score=True, stream=None):
+    def tune_launch(self, wins, anom, cls, active=None, score=True, stream=None, inputs="host", labels=None):
         """``tune`` up to its device work, launched on ``stream`` (default: the
         current one); returns the function that waits for it and returns what
         ``tune`` would (``backprop``'s ``defer``, for a fleet: the fleet plugin
         overlaps the tuning graph with train_gan's host simulators).  Calls
         with disjoint ``active`` sets and different window counts may be
         launched before any is finished; finish them in launch order, then
-        ``sync_state_rows`` if more than one was in flight."""
-        n = np.asarray(wins).shape[1]
+        ``sync_state_rows`` if more than one was in flight.
+
+        ``inputs="device", labels=(y, cls)``: the windows and labels are what
+        ``dataset`` wrote into the graph's W / Y / C for this window count and
+        score mode (``wins`` / ``anom`` / ``cls`` are not read); y / cls
+        [M,n,H] are their downloaded copy, from which the AdamW table and the
+        host scores are built (``labels=(y, cls, positive)``: the table from
+        the dataset's ``positive`` [M,n] instead of ``y.any(axis=2)``).  Only
+        the staging from ``sched`` on is uploaded, as one copy.  Returns what
+        the host form returns."""
+        if inputs not in ("host", "device"):
+            raise ValueError(f'inputs: "host" or "device", not {inputs!r}')
+        device_inputs, positive = inputs == "device", None
+        if device_inputs:
+            if labels is None:
+                raise ValueError('inputs="device" needs labels=(y, cls), the dataset\'s downloaded labels')
+            anom, cls, positive = labels if len(labels) == 3 else (*labels, None)
+        n = np.asarray(anom if device_inputs else wins).shape[1]
         if n == 0:
             res = [(([], None) if score else []) for _ in range(self.M)]
             return lambda: res
         g = self.graph(n, score)
-        anom, cls, act = self.stage(g, wins, anom, cls, active)
+        anom, cls, act = self.stage(g, wins, anom, cls, active, device_inputs, positive)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
         with torch.cuda.stream(st):
-            g.din.copy_(g.hin, non_blocking=True)
+            if device_inputs:
+                o = g.span["sched"][0]
+                g.din[o:].copy_(g.hin[o:], non_blocking=True)
+            else:
+                g.din.copy_(g.hin, non_blocking=True)
             g.graph.replay()
             g.hout.copy_(g.down, non_blocking=True)
 
@@ -2199,6 +2290,61 @@ class FleetTuner:
         the rows they were staged with."""
         for c in cells:
             self.state_dev[c].copy_(torch.from_numpy(self.states[c].vector()))
+
+    # ---------------- the cells' datasets, written on the device ----------------
+    def dataset_io(self, n: int, score=True, capture: bool = True) -> _FleetData:
+        """The dataset buffers of ``graph(n, score)`` (made on first use): a
+        caller may fill ``.series`` [M,n,3H], the pinned staging, itself and
+        call ``dataset(n, None, ...)``."""
+        g = self.graph(n, score, capture)
+        if g.data is None:
+            g.data = _FleetData(self, g)
+        return g.data
+
+    def dataset(self, n: int, series, train_max=None, active=None, score=True, capture: bool = True) -> _FleetData:
+        """``on_the_fly_dataset_many`` on the device (``pgp_tune_dataset_cells``)
+        for the active cells, written where the tuning graph reads it: series
+        [M,n,3H] fp64 = each cell's last n rows of stats.time_series (None: the
+        rows already in ``dataset_io(n, score).series``), train_max [M,3H] fp64
+        = each cell's np.max(train_time_data, axis=0), uploaded when it is not
+        the array of the previous call (None: keep that one).  One upload from
+        pinned memory (series | active), one launch: windows / y / cls go into
+        ``graph(n, score)``'s W / Y / C, ``positive`` beside them, and the
+        active cells' inference windows into ``self.infer_windows`` [M,3,3H]
+        (``detect``'s input; calls for different n with disjoint active sets
+        fill it between them).  The labels' download (y | cls, positive) is
+        enqueued behind the launch and NOT waited for: the returned buffers'
+        ``y`` / ``cls`` / ``positive`` hold it once the current stream has been
+        synchronised (``detect_numpy`` does), and ``tune_launch(inputs="device",
+        labels=(d.y, d.cls))`` tunes on it.  An inactive cell's rows of every
+        output are left as they were."""
+        M, H, dev = self.M, self.H, self.device
+        n = int(n)
+        if not 1 <= n <= 16:
+            raise ValueError(f"dataset: 1 <= n <= 16 rows, not {n}")
+        d = self.dataset_io(n, score, capture)
+        g = self.graph(n, score, capture)
+        if train_max is not None and train_max is not self._train_max_src:
+            tm = np.ascontiguousarray(train_max, dtype=np.float64)
+            if tm.shape != (M, 3 * H):
+                raise ValueError(f"train_max must be [{M},{3 * H}], not {tm.shape}")
+            self._train_max = torch.from_numpy(tm).to(dev)
+            self._train_max_src = train_max
+        if self._train_max is None:
+            raise ValueError("dataset: no train_max yet")
+        if self.infer_windows is None:
+            self.infer_windows = torch.zeros((M, 3, 3 * H), dtype=torch.float32, device=dev)
+        if series is not None:
+            d.series[...] = np.asarray(series, dtype=np.float64).reshape(M, n, 3 * H)
+        d.hviews["active"][...] = 1 if active is None else np.asarray(active, dtype=bool).reshape(M)
+        d.din.copy_(d.hin, non_blocking=True)
+        _native.check(self._L.pgp_tune_dataset_cells(
+            H, M, n, d.d_active.data_ptr(), d.d_series.data_ptr(), self._train_max.data_ptr(), g.W.data_ptr(),
+            g.Y.data_ptr(), g.C.data_ptr(), d.d_positive.data_ptr(), self.infer_windows.data_ptr(), self._stream()),
+            "pgp_tune_dataset_cells")
+        d.hlabels.copy_(d.labels, non_blocking=True)
+        d.hpositive.copy_(d.d_positive, non_blocking=True)
+        return d
 
     # ---------------- the per-cell GAN step ----------------
     def gan_forward_many(self, g: _FleetGanGraph):
