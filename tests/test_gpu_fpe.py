@@ -91,6 +91,69 @@ def test_fpe_synthetic_vs_oracle(H, B):
     assert_parity(g, r, w, sched, check_latent=False)
 
 
+def _gen_in_band(got, ref, w, sched):
+    """Per generator decision [B,C]: whether the oracle's margin lies inside its
+    derived fp32 bound for these outputs (tests/decision_bounds.py, kind gen);
+    and per window [B] whether its anomaly flags are the oracle's (the bound
+    takes equal flags: DB.compare leaves the other windows out too)."""
+    from tests import decision_bounds as DB
+    ref_an = ref["logits"][..., 1] > ref["logits"][..., 0]
+    got_an = got["logits"][..., 1] > got["logits"][..., 0]
+    ok = (ref_an == got_an).all(axis=1)
+    emb_ref = np.where(ref_an[..., None], ref["protos"], 0.0)
+    emb_gpu = np.where(got_an[..., None], got["protos"].astype(np.float64), 0.0)
+    dns = DB.gen_ns_bound(w["gen"], emb_ref, emb_gpu, sched)
+    return DB._first_argext_slack(np.asarray(ref["new_sched"], np.float64), dns, largest=True)[1] <= 0, ok
+
+
+@pytest.mark.parametrize("H", [16, 50])
+def test_fpe_split_bf16_gan_vs_fp32_gan(H):
+    """The FPE model's K3 in both forms: pgp_load_weights derives the split-bf16
+    GAN planes for FPE models too, so the PreGAN variant runs pgp_gansplit.hip
+    by default and pgp_gan.hip's fp32 kernel only after gan_split(False).  300
+    windows (a fifth workgroup of four waves, a ragged last wave), one-hot
+    schedules with a dense tail of 40 (three and six products per block in the
+    split form): both forms within tolerance of the fp64 FPE oracle, every
+    decision equal except generator targets in band for both forms, and the
+    two forms really ran (different bits)."""
+    B = 300
+    w = W.synth_fpe_weights(H, seed=11)
+    rng = np.random.Generator(np.random.PCG64(1300 + H))
+    x = rng.uniform(0, 1.2, size=(B, 3, 3 * H)).astype(np.float32)
+    h0 = rng.standard_normal((B, 3)).astype(np.float32)
+    sched = np.zeros((B, H, H), np.float32)
+    sched[np.arange(B)[:, None], np.arange(H)[None, :], rng.integers(0, H, size=(B, H))] = 1.0
+    sched[-40:] = rng.uniform(0, 1, size=(40, H, H)).astype(np.float32)
+    s64 = sched.astype(np.float64)
+    ref = O.forward_fpe(w, x.astype(np.float64), h0.astype(np.float64), s64)
+    m = model(f"gsplit{H}", w, H)
+    try:
+        m.gan_split(True)
+        a = run(m, x, h0, sched)
+        m.gan_split(False)
+        b = run(m, x, h0, sched)
+    finally:
+        m.gan_split(True)
+    ga, r = as_parity(a, ref)
+    gb, _ = as_parity(b, ref)
+    r["sched32"] = sched
+    sta = assert_parity(ga, r, w, s64, check_latent=False)
+    stb = assert_parity(gb, r, w, s64, check_latent=False)
+    for tag, st in (("split", sta), ("fp32", stb)):
+        print("CENSUS", f"fpe-k3 {tag} H={H} B={B}", {k: {f: v[f] for f in ("n", "in_band", "mismatch")}
+                                                     for k, v in st.items() if isinstance(v, dict)},
+              "windows_excluded", st["windows_excluded"])
+    for k in ("keep", "final_target", "any", "cls"):
+        assert np.array_equal(a[k], b[k]), k
+    # generator targets may break an fp32 near-tie either way in either form:
+    # where the forms differ, the decision is in band against the oracle for both
+    differ = a["gen_target"] != b["gen_target"]
+    (band_a, ok_a), (band_b, ok_b) = _gen_in_band(ga, r, w, s64), _gen_in_band(gb, r, w, s64)
+    assert np.array_equal(ok_a, ok_b)       # one K4 feeds both forms
+    assert not (differ & ok_a[:, None] & ~(band_a & band_b)).any(), int(differ.sum())
+    assert not np.array_equal(a["probs"], b["probs"])   # the two forms really ran
+
+
 def test_fpe_edge_inputs():
     """zeros, constant rows (all edge scores equal), large values (softmax
     saturation), negative h0 extremes."""
