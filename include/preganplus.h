@@ -562,6 +562,12 @@ typedef struct {
   float step_size;   /* lr / (1 - beta1^step) for this tensor's new step */
   float bc2_sqrt;    /* sqrt(1 - beta2^step) */
 } pgp_adam_tensor;
+/* torch.optim.AdamW's single-tensor step on fp32 tensors.  The entries that
+ * take beta1 / beta2 as floats (this one, pgp_adamw_table, pgp_adamw_table_many,
+ * pgp_gan_step1, pgp_gan_step1_many) are kept as first exported: they widen the
+ * float exactly, so their moment weights 1 - beta carry beta's fp32 rounding
+ * (0.999f -> 0.0009999871 for torch's 0.001: v 1.29e-5 low).  New code calls the
+ * _d forms declared after pgp_gan_step1_many, which take the betas as doubles. */
 int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
               float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, void* stream);
 /* pgp_adamw with the per-step scalars read from the device: sched [ntensors][3]
@@ -638,6 +644,33 @@ int pgp_gan_step1_many(int n_hosts, int n_cells, const int* active, const float*
                        const float* disc_sched, long long disc_sched_cell_stride, const pgp_adam_tensor* gen_tensors,
                        int n_gen, const float* gen_sched, long long gen_sched_cell_stride, float* workspace,
                        float* probs_gen, float* probs_after, void* stream);
+/* The five AdamW-carrying entries with beta1 / beta2 as doubles: the same
+ * arguments and contracts as the entries without the suffix, but the moment
+ * weights 1 - beta1, 1 - beta2 are formed in double and rounded to fp32 once,
+ * as torch forms them for an fp32 tensor (float(1 - 0.999) = 0.001).  The
+ * float-beta entry equals its _d form called with (double)(float)beta. */
+int pgp_adamw_d(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+                double beta1, double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, void* stream);
+int pgp_adamw_table_d(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+                      double beta1, double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors,
+                      const float* sched, void* stream);
+int pgp_adamw_table_many_d(int n_cells, long long slot_len, const int* active, float* P, const float* G,
+                           float* exp_avg, float* exp_avg_sq, float lr, float weight_decay, double beta1,
+                           double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, const float* sched,
+                           long long sched_cell_stride, void* stream);
+int pgp_gan_step1_d(int n_hosts, const float* target, float* P, float* G, float* exp_avg, float* exp_avg_sq,
+                    float lr_disc, float lr_gen, float weight_decay, double beta1, double beta2, float eps,
+                    const pgp_adam_tensor* disc_tensors, int n_disc, const float* disc_sched,
+                    const pgp_adam_tensor* gen_tensors, int n_gen, const float* gen_sched, float* workspace,
+                    float* probs_gen, float* probs_after, void* stream);
+int pgp_gan_step1_many_d(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
+                         float* exp_avg, float* exp_avg_sq, float lr_disc, float lr_gen, float weight_decay,
+                         double beta1, double beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
+                         const float* disc_sched, long long disc_sched_cell_stride,
+                         const pgp_adam_tensor* gen_tensors, int n_gen, const float* gen_sched,
+                         long long gen_sched_cell_stride, float* workspace, float* probs_gen, float* probs_after,
+                         void* stream);
+
 
 /* ---------------------------------------------------------------------------
  * The whole online training step of run_model in ONE call (BASELINE config

@@ -131,6 +131,15 @@ SIGNATURES = {
     "pgp_gan_forward1_many": (i32, [i32, i32] + [vp] * 7 + [stream]),
     "pgp_gan_step1_many": (i32, [i32, i32] + [vp] * 6 + [f32] * 6 + [adam, i32, vp, i64] + [adam, i32, vp, i64]
                            + [vp] * 3 + [stream]),
+    # the same five with beta1 / beta2 as doubles (1 - beta rounded once, torch's moment weights): what this package calls
+    "pgp_adamw_d": (i32, [vp] * 4 + [f32, f32, f64, f64, f32] + [adam, i32, stream]),
+    "pgp_adamw_table_d": (i32, [vp] * 4 + [f32, f32, f64, f64, f32] + [adam, i32, vp, stream]),
+    "pgp_adamw_table_many_d": (i32, [i32, i64, vp] + [vp] * 4 + [f32, f32, f64, f64, f32]
+                               + [adam, i32, vp, i64, stream]),
+    "pgp_gan_step1_d": (i32, [i32] + [vp] * 5 + [f32, f32, f32, f64, f64, f32] + [adam, i32, vp] + [adam, i32, vp]
+                        + [vp] * 3 + [stream]),
+    "pgp_gan_step1_many_d": (i32, [i32, i32] + [vp] * 6 + [f32, f32, f32, f64, f64, f32] + [adam, i32, vp, i64]
+                             + [adam, i32, vp, i64] + [vp] * 3 + [stream]),
     "pgp_online_create": (i32, [ctypes.POINTER(_OnlineDesc), pvp]),
     "pgp_online_destroy": (i32, [vp]),
     "pgp_online_step": (i32, [vp, stream, stream, _COLL_FN, vp]),

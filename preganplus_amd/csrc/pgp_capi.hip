@@ -853,7 +853,7 @@ int pgp_gan_forward1(int n_hosts, const float* emb, const float* sched, const fl
   return PGP_OK;
 }
 
-static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float lr, float wd, float b1, float b2,
+static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float lr, float wd, double b1, double b2,
                       float eps, const pgp_adam_tensor* t, int n, const float* sched, long lo, long hi) {
   if (!t || !sched || n < 0 || n > kMaxTensors) return false;
   *a = AdamArgs{};
@@ -862,8 +862,9 @@ static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float
   a->m = m;
   a->v = v;
   a->lr_wd = lr * wd;
-  a->b1 = b1;
-  a->b2 = b2;
+  a->b2 = (float)b2;
+  a->omb1 = adam_moment_weight(b1);
+  a->omb2 = adam_moment_weight(b2);
   a->eps = eps;
   a->ntensors = n;
   a->sched = sched;
@@ -876,8 +877,8 @@ static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float
   return true;
 }
 
-int pgp_gan_step1(int n_hosts, const float* target, float* P, float* G, float* exp_avg, float* exp_avg_sq,
-                  float lr_disc, float lr_gen, float weight_decay, float beta1, float beta2, float eps,
+int pgp_gan_step1_d(int n_hosts, const float* target, float* P, float* G, float* exp_avg, float* exp_avg_sq,
+                  float lr_disc, float lr_gen, float weight_decay, double beta1, double beta2, float eps,
                   const pgp_adam_tensor* disc_tensors, int n_disc, const float* disc_sched,
                   const pgp_adam_tensor* gen_tensors, int n_gen, const float* gen_sched, float* workspace,
                   float* probs_gen, float* probs_after, void* stream) {
@@ -913,9 +914,9 @@ int pgp_gan_forward1_many(int n_hosts, int n_cells, const int* active, const flo
   return PGP_OK;
 }
 
-int pgp_gan_step1_many(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
+int pgp_gan_step1_many_d(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
                        float* exp_avg, float* exp_avg_sq, float lr_disc, float lr_gen, float weight_decay,
-                       float beta1, float beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
+                       double beta1, double beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
                        const float* disc_sched, long long disc_sched_cell_stride, const pgp_adam_tensor* gen_tensors,
                        int n_gen, const float* gen_sched, long long gen_sched_cell_stride, float* workspace,
                        float* probs_gen, float* probs_after, void* stream) {
@@ -951,8 +952,8 @@ int pgp_gan_probs(int n_hosts, int batch, const float* workspace, float* probs, 
   return PGP_OK;
 }
 
-int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
-              float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, void* stream) {
+int pgp_adamw_d(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+              double beta1, double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, void* stream) {
   if (!P || !G || !exp_avg || !exp_avg_sq || !tensors || ntensors < 0 || ntensors > kMaxTensors)
     return fail(PGP_ERR_ARG, "bad adamw arguments");
   if (ntensors == 0) return PGP_OK;
@@ -962,8 +963,9 @@ int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float
   a.m = exp_avg;
   a.v = exp_avg_sq;
   a.lr_wd = lr * weight_decay;
-  a.b1 = beta1;
-  a.b2 = beta2;
+  a.b2 = (float)beta2;
+  a.omb1 = adam_moment_weight(beta1);
+  a.omb2 = adam_moment_weight(beta2);
   a.eps = eps;
   a.ntensors = ntensors;
   for (int i = 0; i < ntensors; ++i) {
@@ -977,8 +979,8 @@ int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float
   return PGP_OK;
 }
 
-int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
-                    float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors,
+int pgp_adamw_table_d(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+                    double beta1, double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors,
                     const float* sched, void* stream) {
   if (!P || !G || !exp_avg || !exp_avg_sq || !tensors || !sched || ntensors < 0 || ntensors > kMaxTensors)
     return fail(PGP_ERR_ARG, "bad adamw arguments");
@@ -989,8 +991,9 @@ int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq,
   a.m = exp_avg;
   a.v = exp_avg_sq;
   a.lr_wd = lr * weight_decay;
-  a.b1 = beta1;
-  a.b2 = beta2;
+  a.b2 = (float)beta2;
+  a.omb1 = adam_moment_weight(beta1);
+  a.omb2 = adam_moment_weight(beta2);
   a.eps = eps;
   a.ntensors = ntensors;
   a.sched = sched;
@@ -1007,8 +1010,8 @@ int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq,
 
 // pgp_adamw_table on every active slot of a fleet (each cell its own optimizer, utils.py:65, stepped after its
 // own backward, recovery/PreGANSrc/src/train.py:51-54)
-int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, float* P, const float* G, float* exp_avg,
-                         float* exp_avg_sq, float lr, float weight_decay, float beta1, float beta2, float eps,
+int pgp_adamw_table_many_d(int n_cells, long long slot_len, const int* active, float* P, const float* G, float* exp_avg,
+                         float* exp_avg_sq, float lr, float weight_decay, double beta1, double beta2, float eps,
                          const pgp_adam_tensor* tensors, int ntensors, const float* sched,
                          long long sched_cell_stride, void* stream) {
   if (n_cells < 0 || ntensors < 0 || ntensors > kMaxTensors || slot_len < 0 || sched_cell_stride < 0)
@@ -1024,8 +1027,9 @@ int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, flo
   a.m = exp_avg;
   a.v = exp_avg_sq;
   a.lr_wd = lr * weight_decay;
-  a.b1 = beta1;
-  a.b2 = beta2;
+  a.b2 = (float)beta2;
+  a.omb1 = adam_moment_weight(beta1);
+  a.omb2 = adam_moment_weight(beta2);
   a.eps = eps;
   a.ntensors = ntensors;
   a.sched = sched;
@@ -1039,6 +1043,47 @@ int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, flo
   HIPCHK(launch_adamw_cells(a, n_cells, (long)slot_len, active, (long)sched_cell_stride,
                             reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;
+}
+
+// ---- the float-beta forms of the five entries above, kept as they were exported before the _d forms: beta
+// widened exactly, so 1 - beta carries the fp32 rounding of beta (0.999f -> 0.0009999871) ----
+int pgp_adamw(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+              float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors, void* stream) {
+  return pgp_adamw_d(P, G, exp_avg, exp_avg_sq, lr, weight_decay, (double)beta1, (double)beta2, eps, tensors, ntensors,
+                     stream);
+}
+int pgp_adamw_table(float* P, const float* G, float* exp_avg, float* exp_avg_sq, float lr, float weight_decay,
+                    float beta1, float beta2, float eps, const pgp_adam_tensor* tensors, int ntensors,
+                    const float* sched, void* stream) {
+  return pgp_adamw_table_d(P, G, exp_avg, exp_avg_sq, lr, weight_decay, (double)beta1, (double)beta2, eps, tensors,
+                           ntensors, sched, stream);
+}
+int pgp_adamw_table_many(int n_cells, long long slot_len, const int* active, float* P, const float* G, float* exp_avg,
+                         float* exp_avg_sq, float lr, float weight_decay, float beta1, float beta2, float eps,
+                         const pgp_adam_tensor* tensors, int ntensors, const float* sched,
+                         long long sched_cell_stride, void* stream) {
+  return pgp_adamw_table_many_d(n_cells, slot_len, active, P, G, exp_avg, exp_avg_sq, lr, weight_decay, (double)beta1,
+                                (double)beta2, eps, tensors, ntensors, sched, sched_cell_stride, stream);
+}
+int pgp_gan_step1(int n_hosts, const float* target, float* P, float* G, float* exp_avg, float* exp_avg_sq,
+                  float lr_disc, float lr_gen, float weight_decay, float beta1, float beta2, float eps,
+                  const pgp_adam_tensor* disc_tensors, int n_disc, const float* disc_sched,
+                  const pgp_adam_tensor* gen_tensors, int n_gen, const float* gen_sched, float* workspace,
+                  float* probs_gen, float* probs_after, void* stream) {
+  return pgp_gan_step1_d(n_hosts, target, P, G, exp_avg, exp_avg_sq, lr_disc, lr_gen, weight_decay, (double)beta1,
+                         (double)beta2, eps, disc_tensors, n_disc, disc_sched, gen_tensors, n_gen, gen_sched,
+                         workspace, probs_gen, probs_after, stream);
+}
+int pgp_gan_step1_many(int n_hosts, int n_cells, const int* active, const float* target, float* P, float* G,
+                       float* exp_avg, float* exp_avg_sq, float lr_disc, float lr_gen, float weight_decay,
+                       float beta1, float beta2, float eps, const pgp_adam_tensor* disc_tensors, int n_disc,
+                       const float* disc_sched, long long disc_sched_cell_stride, const pgp_adam_tensor* gen_tensors,
+                       int n_gen, const float* gen_sched, long long gen_sched_cell_stride, float* workspace,
+                       float* probs_gen, float* probs_after, void* stream) {
+  return pgp_gan_step1_many_d(n_hosts, n_cells, active, target, P, G, exp_avg, exp_avg_sq, lr_disc, lr_gen,
+                              weight_decay, (double)beta1, (double)beta2, eps, disc_tensors, n_disc, disc_sched,
+                              disc_sched_cell_stride, gen_tensors, n_gen, gen_sched, gen_sched_cell_stride, workspace,
+                              probs_gen, probs_after, stream);
 }
 
 int pgp_repack_master(pgp_model* m, const float* P_device, const double* prototypes_device, void* stream) {

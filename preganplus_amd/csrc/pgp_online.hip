@@ -208,7 +208,7 @@ bool fuse_adam(const pgp_online* o, int sec, AdamFuse* f) {
     if (a.t[i].step_size != a.t[0].step_size || a.t[i].bc2_sqrt != a.t[0].bc2_sqrt ||
         (a.t[i].active & kAdamFromTable))
       return false;
-  *f = AdamFuse{a.param, a.m, a.v, a.grad, a.lr_wd, a.b1, a.b2, a.eps, a.t[0].step_size, a.t[0].bc2_sqrt};
+  *f = AdamFuse{a.param, a.m, a.v, a.grad, a.lr_wd, a.b2, a.eps, a.t[0].step_size, a.t[0].bc2_sqrt, a.omb1, a.omb2};
   return true;
 }
 
@@ -311,8 +311,9 @@ int pgp_online_create(const pgp_online_desc* desc, pgp_online** out) {
     a.m = d.exp_avg;
     a.v = d.exp_avg_sq;
     a.lr_wd = (float)d.lr[s] * (float)d.weight_decay;  // pgp_adamw_table's (float lr) * (float wd)
-    a.b1 = (float)d.beta1;
     a.b2 = (float)d.beta2;
+    a.omb1 = adam_moment_weight(d.beta1);
+    a.omb2 = adam_moment_weight(d.beta2);
     a.eps = (float)d.eps;
     a.ntensors = 0;
     a.sched = s == kTr ? d.adam_rows : nullptr;

@@ -71,7 +71,8 @@ struct AdamArgs {
   float* m;
   float* v;
   float lr_wd;  // lr * weight_decay
-  float b1, b2, eps;
+  float b2, eps;     // beta1 itself is not needed on the device: only 1 - beta1 enters the update
+  float omb1, omb2;  // the moment weights 1 - beta1, 1 - beta2: formed in double on the host, rounded once
   int ntensors;
   const float* sched;  // optional device table [ntensors][3] = (active, step_size, bc2_sqrt), overrides t[]
   AdamTensor t[kMaxTensors];
@@ -81,6 +82,11 @@ struct AdamArgs {
 // p *= 1 - lr*wd; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  Shared by the batched kernel
 // (pgp_train.hip) and the fused batch-1 GAN step (pgp_gan1.hip).
+// The moment weights are torch's on an fp32 tensor: the python doubles 1 - beta
+// rounded once, float(1 - 0.999) = 0.001 (adam_moment_weight below); formed in
+// fp32, 1.0f - 0.999f = 0.0009999871 leaves v 1.29e-5 low and every update 108
+// half-ulps of itself off (tests/adamw_replay.py holds the update to ~10).
+inline float adam_moment_weight(double beta) { return (float)(1.0 - beta); }
 // One section's AdamW fused into the kernel that writes its gradients (the
 // batched GAN step's weight-gradient kernel, world size 1: no all-reduce
 // between gradient and update): every tensor of the section with the same
@@ -90,31 +96,33 @@ struct AdamFuse {
   float* m;
   float* v;
   const float* G;  // the gradient buffer the kernel writes (element o of G updates P[o])
-  float lr_wd, b1, b2, eps, step_size, bc2_sqrt;
+  float lr_wd, b2, eps, step_size, bc2_sqrt;
+  float omb1, omb2;  // as AdamArgs'
 };
 #ifdef __HIP__
 __device__ __forceinline__ void adamw_update(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
-                                             long o, float g, float lr_wd, float b1, float b2, float eps,
-                                             float step_size, float bc2_sqrt) {
+                                             long o, float g, float lr_wd, float omb1, float b2, float omb2,
+                                             float eps, float step_size, float bc2_sqrt) {
   float p = P[o] * (1.0f - lr_wd);
-  const float m = M[o] + (1.0f - b1) * (g - M[o]);
-  const float v = b2 * V[o] + (1.0f - b2) * g * g;
+  const float m = M[o] + omb1 * (g - M[o]);
+  const float v = b2 * V[o] + omb2 * g * g;
   p -= step_size * m / (sqrtf(v) / bc2_sqrt + eps);
   P[o] = p;
   M[o] = m;
   V[o] = v;
 }
 __device__ __forceinline__ void adamw_elem(const AdamArgs& a, long o, float step_size, float bc2_sqrt) {
-  adamw_update(a.param, a.m, a.v, o, a.grad[o], a.lr_wd, a.b1, a.b2, a.eps, step_size, bc2_sqrt);
+  adamw_update(a.param, a.m, a.v, o, a.grad[o], a.lr_wd, a.omb1, a.b2, a.omb2, a.eps, step_size, bc2_sqrt);
 }
 // adamw_elem on the slot that starts `slot` floats into a's four buffers (the cell-indexed kernel)
 __device__ __forceinline__ void adamw_elem_slot(const AdamArgs& a, long slot, long o, float step_size,
                                                 float bc2_sqrt) {
-  adamw_update(a.param + slot, a.m + slot, a.v + slot, o, a.grad[slot + o], a.lr_wd, a.b1, a.b2, a.eps, step_size,
-               bc2_sqrt);
+  adamw_update(a.param + slot, a.m + slot, a.v + slot, o, a.grad[slot + o], a.lr_wd, a.omb1, a.b2, a.omb2, a.eps,
+               step_size, bc2_sqrt);
 }
 __device__ __forceinline__ void adamw_fused(const AdamFuse& f, const float* g_at, float g) {
-  if (f.P) adamw_update(f.P, f.m, f.v, g_at - f.G, g, f.lr_wd, f.b1, f.b2, f.eps, f.step_size, f.bc2_sqrt);
+  if (f.P)
+    adamw_update(f.P, f.m, f.v, g_at - f.G, g, f.lr_wd, f.omb1, f.b2, f.omb2, f.eps, f.step_size, f.bc2_sqrt);
 }
 #endif
 

@@ -85,10 +85,10 @@ class FPETrainer:
             arr.append(_AdamTensor(t["offset"], t["n"], int(active), self.lr / (1 - self.b1 ** st),
                                    math.sqrt(1 - self.b2 ** st)))
         desc = (_AdamTensor * len(arr))(*arr)
-        _native.check(self._L.pgp_adamw(
+        _native.check(self._L.pgp_adamw_d(
             ctypes.c_void_p(self.P.data_ptr()), ctypes.c_void_p(self.G.data_ptr()),
             ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
-            self.lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw")
+            self.lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw_d")
 
     def backprop(self, st: TuneState, wins, h0s, anom, cls):
         """train.py:42-57 over the windows: one device step per window (forward,

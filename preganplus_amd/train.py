@@ -375,11 +375,11 @@ class Trainer:
         the updated Disc + AdamW (tabG), the updated GAN's probabilities.
         target [2] device fp32; probs_gen / probs_after [2] device outputs."""
         desc = lambda sel: (_AdamTensor * len(sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in sel])
-        _native.check(self._L.pgp_gan_step1(
+        _native.check(self._L.pgp_gan_step1_d(
             self.H, target.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
             self.lrs["disc"], self.lrs["gen"], self.wd, self.b1, self.b2, self.eps,
             desc(selD), len(selD), tabD.data_ptr(), desc(selG), len(selG), tabG.data_ptr(),
-            self.gscr.data_ptr(), probs_gen.data_ptr(), probs_after.data_ptr(), self._stream()), "pgp_gan_step1")
+            self.gscr.data_ptr(), probs_gen.data_ptr(), probs_after.data_ptr(), self._stream()), "pgp_gan_step1_d")
 
     def gan_disc_backward(self, target):
         """The Disc's BCE gradients toward target [B,2], WRITTEN into G's disc
@@ -421,10 +421,10 @@ class Trainer:
             arr.append(_AdamTensor(t["offset"], t["n"], int(active), lr / (1 - self.b1 ** st),
                                    math.sqrt(1 - self.b2 ** st)))
         desc = (_AdamTensor * len(arr))(*arr)
-        _native.check(self._L.pgp_adamw(
+        _native.check(self._L.pgp_adamw_d(
             ctypes.c_void_p(self.P.data_ptr()), ctypes.c_void_p(self.G.data_ptr()),
             ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
-            lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw")
+            lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw_d")
 
     def adam_schedule(self, section: str, inactive_per_step):
         """adam_step's host bookkeeping for a sequence of steps, done ahead:
@@ -468,11 +468,11 @@ class Trainer:
         """AdamW over `sel` with the per-step scalars in the device row `sched`
         [T,3] (``pgp_adamw_table``): fixed kernel arguments, graph-capturable."""
         desc = self._adam_desc(sel)
-        _native.check(self._L.pgp_adamw_table(
+        _native.check(self._L.pgp_adamw_table_d(
             ctypes.c_void_p(self.P.data_ptr()), ctypes.c_void_p(self.G.data_ptr()),
             ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
             self.lrs[section], self.wd, self.b1, self.b2, self.eps, desc, len(sel), sched.data_ptr(),
-            self._stream()), "pgp_adamw_table")
+            self._stream()), "pgp_adamw_table_d")
 
     def all_reduce_grads(self, section: str, group=None):
         """Data-parallel tuning: sum the section's gradients over
@@ -2110,10 +2110,10 @@ class FleetTuner:
     def adamw_many(self, g: _FleetGraph, i: int):
         """Step i's AdamW of every active cell from its own table row (``pgp_adamw_table_many``)."""
         T = len(self.sel)
-        _native.check(self._L.pgp_adamw_table_many(
+        _native.check(self._L.pgp_adamw_table_many_d(
             self.M, self.slot_len, g.active.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), self.m.data_ptr(),
             self.v.data_ptr(), self.lrs["transformer"], self.wd, self.b1, self.b2, self.eps, self._desc, T,
-            g.sched.data_ptr() + 4 * 3 * T * i, g.n * T * 3, self._stream()), "pgp_adamw_table_many")
+            g.sched.data_ptr() + 4 * 3 * T * i, g.n * T * 3, self._stream()), "pgp_adamw_table_many_d")
 
     def forward_cells(self, g: _FleetGraph):
         """accuracy()'s forward of every active cell on its own windows (``pgp_tune_forward_cells``)."""
@@ -2355,13 +2355,13 @@ class FleetTuner:
 
     def gan_step_many(self, g: _FleetGanGraph):
         """The rest of train_gan for every active cell from its own table rows (``pgp_gan_step1_many``)."""
-        _native.check(self._L.pgp_gan_step1_many(
+        _native.check(self._L.pgp_gan_step1_many_d(
             self.H, self.M, g.active.data_ptr(), g.target.data_ptr(), self.P.data_ptr(), self.G.data_ptr(),
             self.m.data_ptr(), self.v.data_ptr(), self.lrs["disc"], self.lrs["gen"], self.wd, self.b1, self.b2,
             self.eps, self._descD, len(self.selD), g.tabD.data_ptr(), 3 * len(self.selD),
             self._descG, len(self.selG), g.tabG.data_ptr(), 3 * len(self.selG),
             g.gscr.data_ptr(), g.probs_gen.data_ptr(), g.probs_after.data_ptr(), self._stream()),
-            "pgp_gan_step1_many")
+            "pgp_gan_step1_many_d")
 
     def gan_graph(self, envs: bool = False) -> _FleetGanGraph:
         """train_gan's buffers and graphs, cached per mode (captured on first use)."""

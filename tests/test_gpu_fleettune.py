@@ -218,9 +218,9 @@ def test_graph_equals_eager_entries(H, p):
             H, K, M, n, i, ptr(g.active), ptr(g.W), ptr(g.Y), ptr(g.C), ptr(b.P), ptr(b.G), ptr(g.state),
             TR.PROTO_UPDATE_MIN, TR.PROTO_FACTOR_DECAY, ptr(b.logits), ptr(b.protos), ptr(g.dout), p, ptr(g.rng),
             b._stream()), "pgp_tune_step1_many")
-        _native.check(L.pgp_adamw_table_many(
+        _native.check(L.pgp_adamw_table_many_d(    # the entry the graph holds (the betas as doubles)
             M, b.slot_len, ptr(g.active), ptr(b.P), ptr(b.G), ptr(b.m), ptr(b.v), b.lrs["transformer"], b.wd, b.b1,
-            b.b2, b.eps, b._desc, T, ptr(g.sched[:, i]), n * T * 3, b._stream()), "pgp_adamw_table_many")
+            b.b2, b.eps, b._desc, T, ptr(g.sched[:, i]), n * T * 3, b._stream()), "pgp_adamw_table_many_d")
     g.dout[g.o_state:g.o_lg].copy_(g.state.view(-1))
     _native.check(L.pgp_tune_forward_cells(H, M, n, ptr(g.active), ptr(g.W), ptr(b.P), ptr(g.dout[g.o_lg:]),
                                            ptr(g.dout[g.o_pr:]), b._stream()), "pgp_tune_forward_cells")

@@ -6,7 +6,8 @@ framework series, and every GRU state the forwards drew.  fp32 device training
 vs the fp64 reference: parameters after each epoch within fp32 tolerance (the
 AdamW rule of the tuning tests: entries whose gradient is rounding noise take
 an lr-sized step of either sign), prototypes / factor / counters / scores from
-the same bookkeeping."""
+the same bookkeeping.  The AdamW update itself is pinned without that waiver by
+tests/test_gpu_adamw_fused.py::test_fpe_step_replays."""
 import numpy as np
 import pytest
 import torch

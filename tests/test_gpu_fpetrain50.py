@@ -176,7 +176,8 @@ def _cscore_within_decision_bounds(ft, st, z, ep, wins, anom, cls, csc):
 def test_fpe50_offline_training_epochs_match_reference():
     """test_fpe_offline_training_epochs_match_reference at 50 hosts, through
     FPETrainer(H=50).backprop and accuracy: fp32 device training vs the fp64
-    reference, the same tolerance forms, key-bias exclusion and step counts."""
+    reference, the same tolerance forms, key-bias exclusion and step counts (the
+    AdamW update itself, without them: test_gpu_adamw_fused.py::test_fpe_step_replays)."""
     from preganplus_amd import fpetrain as FT
     from preganplus_amd import train as TR
     z, _, _, init, protos = C.fixture()

@@ -41,7 +41,8 @@ def test_fused_gan_step_matches_eager(scores):
     over 4 consecutive calls: schedules, losses and the gate to fp32 tolerance,
     parameters to within one AdamW step where a gradient element is rounding
     noise around zero (m / sqrt(v) is its sign on the first steps), moments
-    and step counts."""
+    and step counts.  The update itself is pinned, every element and v included,
+    by tests/test_gpu_adamw_fused.py::test_fused_gan_step_replays."""
     from preganplus_amd import train as TR
     w, extra = W.load_npz("preganplus_amd/data/simulator_16.npz")
     z = np.load("tests/golden/gan_h16.npz")
@@ -68,7 +69,8 @@ def test_fused_gan_step_matches_eager(scores):
 
 
 def test_fused_gan_step_h8_matches_eager():
-    """The same at 8 hosts on seeded weights (one-hot schedules, as GOBI's)."""
+    """The same at 8 hosts on seeded weights (one-hot schedules, as GOBI's); the
+    update itself: tests/test_gpu_adamw_fused.py::test_fused_gan_step_replays."""
     from preganplus_amd import train as TR
     H = 8
     w = W.synth_weights(H, seed=4)

@@ -29,7 +29,8 @@ def key_bias_mask(name, n, d=16):
     keys is invariant to a shift q.b_k shared by all keys), so both the fp64
     reference and the fp32 kernels hold rounding noise there, which AdamW turns
     into O(lr) steps of arbitrary sign: those elements are compared with an
-    lr-sized tolerance instead."""
+    lr-sized tolerance instead.  (The update itself is held to its rounding
+    bound on every element, these included, by tests/test_gpu_adamw_fused.py.)"""
     m = np.zeros(n, dtype=bool)
     if name.endswith("self_attn.in_proj_bias"):
         m[d:2 * d] = True
@@ -468,7 +469,8 @@ def _param_close(z, k, steps, rel, abs_scale, lr=1e-4, H=50):
     fp32 gradient's own absolute accuracy (1e-4 of the tensor's largest
     gradient, as the gradient check allows) takes a step whose sign is rounding
     noise on both sides: those entries (and the key bias, see key_bias_mask) are
-    held to 2 lr per step; all others to rel / abs_scale."""
+    held to 2 lr per step; all others to rel / abs_scale.  The update on its
+    own gradient bits has no such waiver: tests/test_gpu_adamw_fused.py."""
     from tests.golden import digest as D
     g = D.parts(z, f"g0/{k}")
 

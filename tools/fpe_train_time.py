@@ -75,7 +75,7 @@ def measure(H, steps, windows, reps):
         for _ in range(steps):
             rc = L.pgp_fpe_train_step(H, 3, win.data_ptr(), h0.data_ptr(), y.data_ptr(), c.data_ptr(), P, G,
                                       state.data_ptr(), TR.PROTO_UPDATE_MIN, 1.0, loss.data_ptr(), stream)
-            rc |= L.pgp_adamw(P, G, m, v, ft.lr, ft.wd, ft.b1, ft.b2, ft.eps, desc, len(arr), stream)
+            rc |= L.pgp_adamw_d(P, G, m, v, ft.lr, ft.wd, ft.b1, ft.b2, ft.eps, desc, len(arr), stream)
             if rc:
                 _native.check(rc, "step")
 
