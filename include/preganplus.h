@@ -790,6 +790,70 @@ int pgp_fpe_train_step(int n_hosts, int n_protos, const float* window, const flo
 int pgp_fpe_forward_many(int n_hosts, int n, const float* windows, const float* h0, const float* P, double* probs,
                          double* protos, void* stream);
 
+/* An epoch per launch, and a fleet of FPEs at once (PreGAN.py:39-49 train_model:
+ * num_epochs x N sequential steps; the reference keeps one FPE per
+ * PreGANRecovery, so a fleet of cells trains one per cell).  H = 16 or 50, any
+ * other H returns PGP_ERR_UNSUPPORTED.
+ * pgp_fpe_train_steps: n sequential steps in ONE launch of one workgroup: step i
+ *   is pgp_fpe_train_step on row i of windows [n,3,3H] / h0 [n,3] / y, cls [n,H]
+ *   (loss [n,2] fp64), then torch.optim.AdamW.step (utils.py:65) over P with
+ *   row i of sched [n][ntensors][3] fp32 = (active, step_size, bc2_sqrt), used as
+ *   pgp_adamw_table_d uses it (`tensors`: offset and n only; ntensors in
+ *   [0, 48]); a tensor whose row has active == 0 keeps P and both moments (the
+ *   prototype decoder on a window without a positive label: torch skips a
+ *   parameter without a gradient).  P, G (the last step's gradient), exp_avg,
+ *   exp_avg_sq, state and loss are left with the bits of the loop that calls,
+ *   for each i, pgp_fpe_train_step on row i and then pgp_adamw_table_d with row
+ *   i of sched; n steps equal n1 + n2 + ... steps on the matching row ranges.
+ *   Fixed summation order, no atomics: the same bits on every run.
+ * pgp_fpe_job: one model's work.  Job m owns slot m of P / G / exp_avg /
+ *   exp_avg_sq ([n_models][pgp_fpe_param_len(H)] floats, contiguous) and row m
+ *   of state [n_models][2K+3].  windows / y / cls are pools of n_pool_windows
+ *   rows; jobs may share a range (a seed sweep over one series).  h0, sched,
+ *   loss (train) and h0, probs, protos (forward) are pools of n_pool_steps
+ *   rows that belong to one job each.
+ * pgp_fpe_train_steps_many: one workgroup per model runs pgp_fpe_train_steps's
+ *   loop on its own slot, state and rows: model m has the bits
+ *   pgp_fpe_train_steps gives with job m's ranges on slot m alone, whatever
+ *   n_models, m's position and the other jobs are.  n == 0 leaves the job's
+ *   slot, state and rows untouched.  n_models is not limited by the device
+ *   (workgroups queue); no workgroup waits for another.
+ * pgp_fpe_forward_many_cells: one workgroup per (model, window): row step_off + i
+ *   of probs / protos [n_pool_steps,H,2] has the bits pgp_fpe_forward_many gives
+ *   window window_off + i with h0 row step_off + i under slot m of P.
+ * jobs: host array [n_models].  jobs_dev: device scratch of n_models *
+ *   sizeof(pgp_fpe_job) bytes that the library fills on `stream` before the
+ *   launch; lifetimes as pgp_gobi_train_steps_many's (`jobs` unchanged until
+ *   the stream has passed the call, jobs_dev until the kernel has ended).
+ * PGP_ERR_ARG before anything is enqueued, all or nothing: a negative n,
+ *   n_models or pool size; n_protos outside [3, 64] (pgp_fpe_train_step's range:
+ *   triplet_loss reads prototypes 0-2); lr <= 0, weight_decay <
+ *   0, eps < 0, a beta outside [0, 1); ntensors outside [0, 48] or a tensor
+ *   outside the slot; in a job reserved != 0, a negative offset, window_off + n
+ *   > n_pool_windows or step_off + n > n_pool_steps; a NULL array while some
+ *   job has n > 0.  n == 0, n_models == 0 or no job with n > 0: PGP_OK,
+ *   nothing launched. */
+typedef struct pgp_fpe_job {
+  long long window_off;  /* first row of the job's dataset in windows / y / cls */
+  long long step_off;    /* first row of the job's h0 / sched / loss (train) or h0 / probs / protos (forward) */
+  int n;                 /* steps (train) or windows (forward); step i uses rows window_off + i and step_off + i */
+  int reserved;          /* 0 */
+} pgp_fpe_job;
+int pgp_fpe_train_steps(int n_hosts, int n_protos, int n, const float* windows, const float* h0, const int* y,
+                        const int* cls, float* P, float* G, float* exp_avg, float* exp_avg_sq, double* state,
+                        double update_min, double decay, float lr, float weight_decay, double beta1, double beta2,
+                        float eps, const pgp_adam_tensor* tensors, int ntensors, const float* sched, double* loss,
+                        void* stream);
+int pgp_fpe_train_steps_many(int n_hosts, int n_protos, int n_models, const pgp_fpe_job* jobs,
+                             long long n_pool_windows, const float* windows, const int* y, const int* cls,
+                             long long n_pool_steps, const float* h0, const float* sched, double* loss, float* P,
+                             float* G, float* exp_avg, float* exp_avg_sq, double* state, double update_min,
+                             double decay, float lr, float weight_decay, double beta1, double beta2, float eps,
+                             const pgp_adam_tensor* tensors, int ntensors, void* jobs_dev, void* stream);
+int pgp_fpe_forward_many_cells(int n_hosts, int n_models, const pgp_fpe_job* jobs, long long n_pool_windows,
+                               const float* windows, long long n_pool_steps, const float* h0, const float* P,
+                               double* probs, double* protos, void* jobs_dev, void* stream);
+
 /* Rebuild the inference layouts from device master weights P (natural fp32)
  * and prototypes [K,2] (host, fp64): the sync after an optimizer step, via the
  * host packer (a device-to-host copy of P, pack, upload; synchronous). */

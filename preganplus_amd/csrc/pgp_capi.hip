@@ -470,6 +470,120 @@ int pgp_fpe_forward_many(int n_hosts, int n, const float* windows, const float* 
   return PGP_OK;
 }
 
+static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float lr, float wd, double b1, double b2,
+                      float eps, const pgp_adam_tensor* t, int n, const float* sched, long lo, long hi);
+
+namespace {
+// what the three cell-indexed FPE entries check of their scalars and of the whole job table, before
+// anything is enqueued; work = some job has n > 0, max_n = the longest job
+int fpe_jobs_check(const std::string& w, int n_hosts, int n_models, const pgp_fpe_job* jobs, long long n_pool_windows,
+                   long long n_pool_steps, bool* work, int* max_n) {
+  *work = false;
+  *max_n = 0;
+  if (fpe_param_count(n_hosts) == 0) return fail(PGP_ERR_UNSUPPORTED, kFpeTrainHosts);
+  if (n_models < 0 || n_pool_windows < 0 || n_pool_steps < 0)
+    return fail(PGP_ERR_ARG, w + ": negative n_models or pool size");
+  if (n_models == 0) return PGP_OK;
+  if (!jobs) return fail(PGP_ERR_ARG, w + ": NULL jobs");
+  for (int m = 0; m < n_models; ++m) {
+    const pgp_fpe_job& j = jobs[m];
+    const std::string at = w + ": job " + std::to_string(m) + ": ";
+    if (j.n < 0 || j.reserved != 0) return fail(PGP_ERR_ARG, at + "negative n or reserved != 0");
+    if (j.window_off < 0 || j.window_off > n_pool_windows || j.n > n_pool_windows - j.window_off)
+      return fail(PGP_ERR_ARG, at + "window range outside the pool");
+    if (j.step_off < 0 || j.step_off > n_pool_steps || j.n > n_pool_steps - j.step_off)
+      return fail(PGP_ERR_ARG, at + "step range outside the pool");
+    if (j.n > 0) *work = true;
+    if (j.n > *max_n) *max_n = j.n;
+  }
+  return PGP_OK;
+}
+// the training entries' scalars and tensor table (offsets relative to the slot)
+int fpe_steps_check(const std::string& w, int n_hosts, int n_protos, float lr, float weight_decay, double beta1,
+                    double beta2, float eps, const pgp_adam_tensor* tensors, int ntensors) {
+  if (fpe_param_count(n_hosts) == 0) return fail(PGP_ERR_UNSUPPORTED, kFpeTrainHosts);
+  if (n_protos < 3 || n_protos > kMaxProtos) return fail(PGP_ERR_ARG, w + ": n_protos outside [3, 64]");
+  if (!(lr > 0.f) || !(weight_decay >= 0.f) || !(eps >= 0.f) || !(beta1 >= 0.0 && beta1 < 1.0) ||
+      !(beta2 >= 0.0 && beta2 < 1.0))
+    return fail(PGP_ERR_ARG, w + ": lr > 0, weight_decay >= 0, eps >= 0, betas in [0, 1)");
+  if (ntensors < 0 || ntensors > kMaxTensors) return fail(PGP_ERR_ARG, w + ": ntensors outside [0, 48]");
+  const long long len = fpe_param_count(n_hosts);
+  for (int i = 0; tensors && i < ntensors; ++i)
+    if (tensors[i].offset < 0 || tensors[i].n < 0 || tensors[i].offset > len || tensors[i].n > len - tensors[i].offset)
+      return fail(PGP_ERR_ARG, w + ": AdamW tensor outside the slot");
+  return PGP_OK;
+}
+}  // namespace
+
+int pgp_fpe_train_steps(int n_hosts, int n_protos, int n, const float* windows, const float* h0, const int* y,
+                        const int* cls, float* P, float* G, float* exp_avg, float* exp_avg_sq, double* state,
+                        double update_min, double decay, float lr, float weight_decay, double beta1, double beta2,
+                        float eps, const pgp_adam_tensor* tensors, int ntensors, const float* sched, double* loss,
+                        void* stream) {
+  const int rc = fpe_steps_check("fpe_train_steps", n_hosts, n_protos, lr, weight_decay, beta1, beta2, eps, tensors,
+                                 ntensors);
+  if (rc != PGP_OK) return rc;
+  if (n < 0) return fail(PGP_ERR_ARG, "fpe_train_steps: negative n");
+  if (n == 0) return PGP_OK;
+  if (!windows || !h0 || !y || !cls || !P || !G || !exp_avg || !exp_avg_sq || !state || !sched || !loss ||
+      (ntensors > 0 && !tensors))
+    return fail(PGP_ERR_ARG, "fpe_train_steps: NULL argument");
+  const pgp_adam_tensor none{};
+  AdamArgs a;
+  if (!adam_args(&a, P, G, exp_avg, exp_avg_sq, lr, weight_decay, beta1, beta2, eps, tensors ? tensors : &none,
+                 ntensors, sched, 0, (long)fpe_param_count(n_hosts)))
+    return fail(PGP_ERR_ARG, "fpe_train_steps: AdamW tensor outside the slot");
+  const pgp_fpe_job one{0, 0, n, 0};
+  HIPCHK(launch_fpe_train_steps_cells(n_hosts, 1, nullptr, one, windows, h0, y, cls, n_protos, state, update_min,
+                                      decay, loss, a, reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_fpe_train_steps_many(int n_hosts, int n_protos, int n_models, const pgp_fpe_job* jobs,
+                             long long n_pool_windows, const float* windows, const int* y, const int* cls,
+                             long long n_pool_steps, const float* h0, const float* sched, double* loss, float* P,
+                             float* G, float* exp_avg, float* exp_avg_sq, double* state, double update_min,
+                             double decay, float lr, float weight_decay, double beta1, double beta2, float eps,
+                             const pgp_adam_tensor* tensors, int ntensors, void* jobs_dev, void* stream) {
+  int rc = fpe_steps_check("fpe_train_steps_many", n_hosts, n_protos, lr, weight_decay, beta1, beta2, eps, tensors,
+                           ntensors);
+  if (rc != PGP_OK) return rc;
+  bool work;
+  int max_n;
+  rc = fpe_jobs_check("fpe_train_steps_many", n_hosts, n_models, jobs, n_pool_windows, n_pool_steps, &work, &max_n);
+  if (rc != PGP_OK || !work) return rc;
+  if (!windows || !h0 || !y || !cls || !P || !G || !exp_avg || !exp_avg_sq || !state || !sched || !loss ||
+      !jobs_dev || (ntensors > 0 && !tensors))
+    return fail(PGP_ERR_ARG, "fpe_train_steps_many: NULL argument");
+  const pgp_adam_tensor none{};
+  AdamArgs a;
+  if (!adam_args(&a, P, G, exp_avg, exp_avg_sq, lr, weight_decay, beta1, beta2, eps, tensors ? tensors : &none,
+                 ntensors, sched, 0, (long)fpe_param_count(n_hosts)))
+    return fail(PGP_ERR_ARG, "fpe_train_steps_many: AdamW tensor outside the slot");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipMemcpyAsync(jobs_dev, jobs, (size_t)n_models * sizeof(pgp_fpe_job), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_fpe_train_steps_cells(n_hosts, n_models, static_cast<const pgp_fpe_job*>(jobs_dev), pgp_fpe_job{},
+                                      windows, h0, y, cls, n_protos, state, update_min, decay, loss, a, st));
+  return PGP_OK;
+}
+
+int pgp_fpe_forward_many_cells(int n_hosts, int n_models, const pgp_fpe_job* jobs, long long n_pool_windows,
+                               const float* windows, long long n_pool_steps, const float* h0, const float* P,
+                               double* probs, double* protos, void* jobs_dev, void* stream) {
+  bool work;
+  int max_n;
+  const int rc = fpe_jobs_check("fpe_forward_many_cells", n_hosts, n_models, jobs, n_pool_windows, n_pool_steps,
+                                &work, &max_n);
+  if (rc != PGP_OK || !work) return rc;
+  if (!windows || !h0 || !P || !probs || !protos || !jobs_dev)
+    return fail(PGP_ERR_ARG, "fpe_forward_many_cells: NULL argument");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipMemcpyAsync(jobs_dev, jobs, (size_t)n_models * sizeof(pgp_fpe_job), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_fpe_forward_cells(n_hosts, n_models, max_n, static_cast<const pgp_fpe_job*>(jobs_dev), windows, h0,
+                                  P, probs, protos, st));
+  return PGP_OK;
+}
+
 static const char* kGobiTrainHosts = "GOBI surrogate training: only energy_latency_16 exists (16 hosts)";
 
 int pgp_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, const float* targets,

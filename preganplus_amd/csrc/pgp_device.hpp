@@ -9,6 +9,7 @@
 #include "pgp_layout.hpp"
 
 struct pgp_gobi_job;  // include/preganplus.h
+struct pgp_fpe_job;
 
 namespace pgp {
 
@@ -82,6 +83,18 @@ hipError_t launch_fpe_step(int n_hosts, const float* win, const float* h0, const
                            double* loss, hipStream_t st);
 hipError_t launch_fpe_forward_many(int n_hosts, int n, const float* wins, const float* h0s, const float* P,
                                    double* probs, double* protos, hipStream_t st);
+// the cell-indexed forms (pgp_fpetrain_cells.hip).  Training: one workgroup per model runs job m's steps, each
+// with its AdamW from a's table, on slot m of a's four buffers and state row m (2K + 3 doubles); jobs_dev
+// [n_models] on the device (already validated), or nullptr with n_models 1: the job `one`.  Forward: one
+// workgroup per (window, model) pair with max_n the longest job, under slot m of P.
+struct AdamArgs;
+hipError_t launch_fpe_train_steps_cells(int n_hosts, int n_models, const pgp_fpe_job* jobs_dev, const pgp_fpe_job& one,
+                                        const float* wins, const float* h0s, const int* ys, const int* clss, int K,
+                                        double* state, double update_min, double decay, double* loss,
+                                        const AdamArgs& a, hipStream_t st);
+hipError_t launch_fpe_forward_cells(int n_hosts, int n_models, int max_n, const pgp_fpe_job* jobs_dev,
+                                    const float* wins, const float* h0s, const float* P, double* probs,
+                                    double* protos, hipStream_t st);
 
 // training of GOBI's surrogate (pgp_gobitrain.hip), 16 hosts: n sequential batch-1 Adam (L2) steps in
 // one launch / n independent per-sample losses.  hipErrorInvalidValue for any other H.

@@ -40,9 +40,17 @@
 //   - every one-thread-per-item phase with more than 256 items is a strided
 //     loop (for_items picks the form from the item count); the others are
 //     covered by the static_asserts in the kernel.
+//
+// The kernel also has a cell-indexed form (template parameter CELLS, above the kernel): a
+// model's whole step loop with its AdamW in one workgroup, one workgroup per model of a fleet
+// (TRAIN), and the forwards of many models in one launch.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "../../include/preganplus.h"
 #include "pgp_device.hpp"
+#include "pgp_train.hpp"
 #include "pgp_tunetargets.hpp"
 
 namespace pgp {
@@ -94,13 +102,42 @@ __device__ __forceinline__ void for_items(int t, F f) {
   }
 }
 
-template <int H_, bool TRAIN>
-__global__ __launch_bounds__(kFT) void fpe_step_kernel(int K, const float* __restrict__ wins,
-                                                       const float* __restrict__ h0s, const int* __restrict__ ys,
-                                                       const int* __restrict__ clss, const float* __restrict__ P,
-                                                       float* __restrict__ G, double* __restrict__ state,
-                                                       double update_min, double decay, double* __restrict__ loss,
-                                                       double* __restrict__ probs_out, double* __restrict__ protos_out) {
+// CELLS (pgp_fpe_train_steps / pgp_fpe_train_steps_many / pgp_fpe_forward_many_cells): the
+// cell-indexed form, instantiated and launched from pgp_fpetrain_cells.hip.
+//   TRAIN: workgroup m is model m.  It runs job m's n steps in sequence on slot m of P / G /
+//     the moments (FP<H>::SIZE floats apart) and on state row m: each step is the step below on
+//     window row window_off + i with h0 / loss row step_off + i, then the AdamW of that step
+//     over the slot (adamw_elem_slot, the code pgp_adamw_table_d runs) from row step_off + i of
+//     the table adam.sched [steps][ntensors][3].  The parameters are rewritten by the kernel
+//     that reads them, and G is read back by the update: both are plain pointers here, so
+//     every parameter read is a vector load that the barriers order against the update's
+//     stores (a scalar load would go through a cache those stores do not update).  A job
+//     without steps returns before the first barrier; the workgroups share nothing they
+//     write and never wait for one another, so any number of them queue on grid x.
+//   forward: workgroup (i, y) is window i of job model0 + y under that model's slot of P; a
+//     job shorter than the grid's width leaves its spare workgroups idle.
+struct FpeCellArgs {
+  const pgp_fpe_job* jobs;  // [models] on the device; nullptr: the one job `one` on slot 0
+  pgp_fpe_job one;
+  int model0;               // forward: the launch's first model (models on grid y)
+  AdamArgs adam;            // TRAIN: param / grad / m / v name slot 0, sched the pool's first row
+};
+template <bool CELLS>
+using FpeCell = std::conditional_t<CELLS, FpeCellArgs, int>;
+template <bool LOOP>
+using FpeParam = std::conditional_t<LOOP, float*, const float* __restrict__>;
+template <bool LOOP>
+using FpeGrad = std::conditional_t<LOOP, float*, float* __restrict__>;
+
+// The looped form at 16 hosts asks for two waves per SIMD (two workgroups per CU: 256 VGPRs, 7 of them spilled
+// in the prologue); at 50 hosts that spills inside the step, so it keeps one.  The other forms: as before.
+template <int H_, bool TRAIN, bool CELLS = false>
+__global__ __launch_bounds__(kFT, TRAIN && CELLS && H_ <= 16 ? 2 : 1)
+void fpe_step_kernel(int K, const float* __restrict__ wins, const float* __restrict__ h0s,
+                     const int* __restrict__ ys, const int* __restrict__ clss, FpeParam<TRAIN && CELLS> Pk,
+                     FpeGrad<TRAIN && CELLS> Gk, double* __restrict__ state, double update_min, double decay,
+                     double* __restrict__ loss, double* __restrict__ probs_out, double* __restrict__ protos_out,
+                     FpeCell<CELLS> cell) {
   using C = FP<H_>;
   constexpr int H = C::H, W = C::W, E = C::E, D = C::D, L = C::L;
   constexpr bool kWide = H > 16;         // the 50-host forms
@@ -109,7 +146,8 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int K, const float* __res
   static_assert(W * H <= kFT && W * D + W * 3 <= kFT && 4 * H <= kFT, "one thread per item");
   static_assert(64 + W * E <= kFT && C::Q <= kFT && C::NF <= kFT && 3 * D <= kFT, "one thread per item");
   const int t = threadIdx.x;
-  const int b = blockIdx.x;  // window (forward-only launches: one per window; training: 0)
+  // window (forward-only launches: one per window; training: 0, the looped form moves the row pointers)
+  const int b = TRAIN && CELLS ? 0 : blockIdx.x;
   const int wv = t >> 6, ln = t & 63;    // wave and lane (kWide: wave w reduces row w)
   const int sg = t / kSub, sl = t % kSub;  // group of kSub lanes and lane in it (kWide: one output per group)
   __shared__ float x[W][C::F];
@@ -143,6 +181,36 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int K, const float* __res
   __shared__ float dsv[W][H], dtv[W][H];
   __shared__ float dav[W][H], ss[W];       // kWide: d a_ij (the same for every j), sum over edges of a . da
 
+  [[maybe_unused]] int steps_left = 1;
+  [[maybe_unused]] long slot = 0;
+  [[maybe_unused]] const float* sched = nullptr;
+  if constexpr (CELLS) {  // the job's rows of the pools and the model's slot
+    const long mdl = TRAIN ? (long)blockIdx.x : (long)cell.model0 + blockIdx.y;
+    const pgp_fpe_job j = cell.jobs ? cell.jobs[mdl] : cell.one;
+    if (TRAIN ? j.n <= 0 : (int)blockIdx.x >= j.n) return;  // uniform over the workgroup, ahead of every barrier
+    wins += j.window_off * (W * C::F);
+    h0s += j.step_off * 3;
+    slot = mdl * C::SIZE;
+    if constexpr (TRAIN) {
+      steps_left = j.n;
+      ys += j.window_off * H;
+      clss += j.window_off * H;
+      state += mdl * (2 * K + 3);
+      loss += j.step_off * 2;
+      sched = cell.adam.sched + j.step_off * (3 * cell.adam.ntensors);
+    } else {
+      probs_out += j.step_off * (2 * H);
+      protos_out += j.step_off * (2 * H);
+    }
+  }
+[[maybe_unused]] next_step:  // TRAIN && CELLS: the job's following steps re-enter here, the row pointers moved on
+  // P / G: the model's slot of the kernel's Pk / Gk (the lone forms: slot 0, Pk / Gk themselves).  The step loop
+  // would let the compiler hoist every per-thread address of P and G out of it (256 VGPRs and 124-190 AGPRs of
+  // parked addresses): an offset it cannot see through keeps that arithmetic inside the step.
+  [[maybe_unused]] long base = slot;
+  if constexpr (TRAIN && CELLS) asm volatile("" : "+v"(base));
+  const auto P = Pk + base;
+  const auto G = Gk + base;
   const float* win = wins + (long)b * W * C::F;
   for (int k = t; k < W * C::F; k += kFT) x[k / C::F][k % C::F] = win[k];
   if (t < 3) hs[0][t] = h0s[(long)b * 3 + t];
@@ -622,9 +690,36 @@ __global__ __launch_bounds__(kFT) void fpe_step_kernel(int K, const float* __res
       G[C::FC + t] = s;
     }
   }
+
+  if constexpr (TRAIN && CELLS) {
+    __syncthreads();  // every element of this step's G is written (by other threads than those that read it now)
+    // ---- torch.optim.AdamW.step of this step, from its row of the table ----
+    const AdamArgs& a = cell.adam;
+    for (int i = 0; i < a.ntensors; ++i) {
+      const float* r = sched + 3 * i;
+      if (r[0] == 0.f) continue;  // no gradient this step: P and both moments stay as they are
+      const float step_size = r[1], bc2_sqrt = r[2];
+      for (int o = t; o < a.t[i].n; o += kFT) adamw_elem_slot(a, slot, a.t[i].off + o, step_size, bc2_sqrt);
+    }
+    if (--steps_left > 0) {  // uniform over the workgroup
+      wins += W * C::F;
+      h0s += 3;
+      ys += H;
+      clss += H;
+      loss += 2;
+      sched += 3 * a.ntensors;
+      __syncthreads();  // the next step reads the updated P and overwrites x
+      goto next_step;
+    }
+  }
 }
 
 }  // namespace
+
+// The cell-indexed instantiations and their launches live in a translation unit of their own
+// (pgp_fpetrain_cells.hip includes this file with PGP_FPE_CELLS_TU), as pgp_gan1_cells.hip's: each
+// unit instantiates one family only, and the four lone kernels are built as before.
+#ifndef PGP_FPE_CELLS_TU
 
 int fpe_param_count(int H) { return H == 16 ? FP<16>::SIZE : H == 50 ? FP<50>::SIZE : 0; }
 
@@ -635,10 +730,10 @@ hipError_t launch_fpe_step(int n_hosts, const float* win, const float* h0, const
                            double* loss, hipStream_t st) {
   if (n_hosts == 16)
     fpe_step_kernel<16, true><<<1, kFT, 0, st>>>(K, win, h0, y, cls, P, G, state, update_min, decay, loss, nullptr,
-                                                 nullptr);
+                                                 nullptr, 0);
   else if (n_hosts == 50)
     fpe_step_kernel<50, true><<<1, kFT, 0, st>>>(K, win, h0, y, cls, P, G, state, update_min, decay, loss, nullptr,
-                                                 nullptr);
+                                                 nullptr, 0);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -648,13 +743,57 @@ hipError_t launch_fpe_forward_many(int n_hosts, int n, const float* wins, const 
                                    double* probs, double* protos, hipStream_t st) {
   if (n_hosts == 16)
     fpe_step_kernel<16, false><<<n, kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr, nullptr, 0.0, 0.0,
-                                                  nullptr, probs, protos);
+                                                  nullptr, probs, protos, 0);
   else if (n_hosts == 50)
     fpe_step_kernel<50, false><<<n, kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr, nullptr, 0.0, 0.0,
-                                                  nullptr, probs, protos);
+                                                  nullptr, probs, protos, 0);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
 }
+
+#else  // PGP_FPE_CELLS_TU
+
+// One workgroup per model on grid x (no cap of its own).  jobs_dev == nullptr: the one job `one` on slot 0
+// (a names slot 0 of P / G / the moments and row 0 of the table pool).  LDS is static here too.
+hipError_t launch_fpe_train_steps_cells(int n_hosts, int n_models, const pgp_fpe_job* jobs_dev, const pgp_fpe_job& one,
+                                        const float* wins, const float* h0s, const int* ys, const int* clss, int K,
+                                        double* state, double update_min, double decay, double* loss,
+                                        const AdamArgs& a, hipStream_t st) {
+  if (n_models <= 0) return hipSuccess;
+  const FpeCellArgs cell{jobs_dev, one, 0, a};
+  if (n_hosts == 16)
+    fpe_step_kernel<16, true, true><<<n_models, kFT, 0, st>>>(K, wins, h0s, ys, clss, a.param, a.grad, state,
+                                                              update_min, decay, loss, nullptr, nullptr, cell);
+  else if (n_hosts == 50)
+    fpe_step_kernel<50, true, true><<<n_models, kFT, 0, st>>>(K, wins, h0s, ys, clss, a.param, a.grad, state,
+                                                              update_min, decay, loss, nullptr, nullptr, cell);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+// workgroup (i, m): window i of job m under slot m of P; max_n the longest job
+hipError_t launch_fpe_forward_cells(int n_hosts, int n_models, int max_n, const pgp_fpe_job* jobs_dev,
+                                    const float* wins, const float* h0s, const float* P, double* probs,
+                                    double* protos, hipStream_t st) {
+  if (n_hosts != 16 && n_hosts != 50) return hipErrorInvalidValue;
+  constexpr int kMaxY = 65535;  // the grid's y limit: more models take more launches
+  for (int m0 = 0; m0 < n_models; m0 += kMaxY) {
+    const int my = n_models - m0 < kMaxY ? n_models - m0 : kMaxY;
+    const FpeCellArgs cell{jobs_dev, pgp_fpe_job{}, m0, AdamArgs{}};
+    if (n_hosts == 16)
+      fpe_step_kernel<16, false, true><<<dim3(max_n, my), kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr,
+                                                                        nullptr, 0.0, 0.0, nullptr, probs, protos, cell);
+    else
+      fpe_step_kernel<50, false, true><<<dim3(max_n, my), kFT, 0, st>>>(3, wins, h0s, nullptr, nullptr, P, nullptr,
+                                                                        nullptr, 0.0, 0.0, nullptr, probs, protos, cell);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+#endif  // PGP_FPE_CELLS_TU
 
 }  // namespace pgp

@@ -808,14 +808,16 @@ class PreGANRecovery(_SaveGan, Recovery):
         self.load_models(weights=weights, extra=extra)
 
     # -- PreGAN.py:39-49 (offline training; the plotter is out of scope) --
-    def train_model(self, fpe, prototypes, time_data, folder=None, num_epochs=None, generator=None):
+    def train_model(self, fpe, prototypes, time_data, folder=None, num_epochs=None, generator=None,
+                    one_launch=False):
         """num_epochs epochs of backprop + accuracy of the FPE on the device
         (preganplus_amd.fpetrain) over load_dataset(time_data) (utils.py:36-42),
         each appending (loss, factor, AScore, CScore) to the FPE's accuracy_list
         and, with a folder, rewriting {env}_FPE_{H}.ckpt (save_model,
         utils.py:49-58).  The GRU states are drawn as the reference's forwards
         draw them (torch.randn, models.py:70), backprop's then accuracy's.
-        Returns the trained FPE weights (fp64 dict) and prototypes."""
+        ``one_launch`` is FPETrainer.backprop's: an epoch's steps in one launch,
+        the same bits.  Returns the trained FPE weights (fp64 dict) and prototypes."""
         from . import fpetrain as FT
         wins, anom, cls = TR.load_dataset(time_data)
         n = len(wins)
@@ -823,7 +825,7 @@ class PreGANRecovery(_SaveGan, Recovery):
         st = TR.TuneState(prototypes)
         for _ in range(NUM_EPOCHS if num_epochs is None else num_epochs):
             self.fpe_epoch += 1
-            losses = ft.backprop(st, wins, FT.draw_h0(n, generator), anom, cls)
+            losses = ft.backprop(st, wins, FT.draw_h0(n, generator), anom, cls, one_launch=one_launch)
             loss = float(np.mean([a for a, _ in losses]) + np.mean([t for _, t in losses]))   # train.py:56-57
             factor = st.factor + TR.PROTO_UPDATE_MIN
             asc, csc = ft.accuracy(st, wins, FT.draw_h0(n, generator), anom, cls)
