@@ -854,6 +854,42 @@ int pgp_fpe_forward_many_cells(int n_hosts, int n_models, const pgp_fpe_job* job
                                const float* windows, long long n_pool_steps, const float* h0, const float* P,
                                double* probs, double* protos, void* jobs_dev, void* stream);
 
+/* PreGANRecovery.run_model's forward (PreGAN.py:97-126: run_encoder, detect :110-111,
+ * embedding + get_classes :119-120, the Gen / Disc gate of recover_decision :74-77) in
+ * ONE workgroup per window, with pgp_forward_fpe's conventions and outputs, straight
+ * from where training keeps the weights: P_fpe is the natural FPE blob
+ * (pgp_fpe_param_len(H) floats, what pgp_fpe_train_steps updates) and P_master a
+ * training master (pgp_master_len(H) floats) whose gen / disc sections (at
+ * pgp_master_offset(H, 1 | 2)) are read; its transformer section is not.  The
+ * prototypes are fp64 on the device and are read as float.  The GAN part runs whether
+ * or not a host is anomalous, so every output is defined.  H = 16 only (where the FPE
+ * kernels, 16 / 50, and the fused batch-1 GAN kernels, 8 / 16, overlap); any other H
+ * returns PGP_ERR_UNSUPPORTED.
+ * Contract of pgp_fpe_forward1_many: cell m's outputs have the bits pgp_fpe_forward1
+ *   gives on slot m's arrays, whatever n_cells, m's position and the other cells are;
+ *   an inactive cell's slots and output rows are neither read nor written; cells are
+ *   grid x (one workgroup each, none waits for another), so n_cells has no cap below
+ *   INT_MAX.  Fixed summation order, no atomics: the same bits on every run.
+ * PGP_ERR_ARG before anything is enqueued: negative n_cells; n_protos outside [1, 64];
+ *   proto_stride < 2 * n_protos; a NULL array (active excepted) with n_cells > 0.
+ *   n_cells == 0: PGP_OK, nothing launched. */
+/* PreGANRecovery.run_model's forward for ONE window (PreGAN.py:97-126) straight from the
+ * natural FPE blob and the training master's gen / disc sections: no packed weights. */
+int pgp_fpe_forward1(int n_hosts, int n_protos, const float* window, const float* h0, const float* sched,
+                     const float* P_fpe, const float* P_master, const double* prototypes_device,
+                     float* scores, float* protos, int* cls, int* any_anom, float* probs, int* keep_orig,
+                     int* final_target, int* gen_target, void* stream);
+/* the same per cell: P_fpe [n_cells][pgp_fpe_param_len(H)], P_master [n_cells][pgp_master_len(H)],
+ * prototypes [n_cells][proto_stride] fp64 (the first 2K doubles of a row: a plain [K][2] row with
+ * stride 2K, or a tuning state row with stride 2K+3), windows [n_cells][3][3H], h0 [n_cells][3],
+ * sched [n_cells][H][H]; outputs as pgp_forward_fpe at batch 1 with a leading n_cells axis;
+ * active [n_cells] int32 or NULL. */
+int pgp_fpe_forward1_many(int n_hosts, int n_protos, int n_cells, const int* active, const float* windows,
+                          const float* h0, const float* sched, const float* P_fpe, const float* P_master,
+                          const double* prototypes, long long proto_stride, float* scores, float* protos,
+                          int* cls, int* any_anom, float* probs, int* keep_orig, int* final_target,
+                          int* gen_target, void* stream);
+
 /* Rebuild the inference layouts from device master weights P (natural fp32)
  * and prototypes [K,2] (host, fp64): the sync after an optimizer step, via the
  * host packer (a device-to-host copy of P, pack, upload; synchronous). */

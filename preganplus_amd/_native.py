@@ -155,6 +155,8 @@ SIGNATURES = {
     "pgp_fpe_train_steps_many": (i32, [i32] * 3 + [vp, i64] + [vp] * 3 + [i64] + [vp] * 8
                                  + [f64, f64, f32, f32, f64, f64, f32] + [adam, i32, vp, stream]),
     "pgp_fpe_forward_many_cells": (i32, [i32, i32, vp, i64, vp, i64] + [vp] * 5 + [stream]),
+    "pgp_fpe_forward1": (i32, [i32, i32] + [vp] * 14 + [stream]),
+    "pgp_fpe_forward1_many": (i32, [i32] * 3 + [vp] * 7 + [i64] + [vp] * 8 + [stream]),
     "pgp_load_weights_master": (i32, [vp, vp, pf64]),
     "pgp_repack_master": (i32, [vp, vp, vp, stream]),
     "pgp_repack_master_sections": (i32, [vp, vp, vp, i32, stream]),

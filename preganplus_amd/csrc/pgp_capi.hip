@@ -584,6 +584,37 @@ int pgp_fpe_forward_many_cells(int n_hosts, int n_models, const pgp_fpe_job* job
   return PGP_OK;
 }
 
+// ---- PreGANRecovery.run_model's forward from the natural FPE blob and the training master
+// (recovery/PreGAN.py:97-126), one window, and per cell for a fleet ----
+int pgp_fpe_forward1_many(int n_hosts, int n_protos, int n_cells, const int* active, const float* windows,
+                          const float* h0, const float* sched, const float* P_fpe, const float* P_master,
+                          const double* prototypes, long long proto_stride, float* scores, float* protos,
+                          int* cls, int* any_anom, float* probs, int* keep_orig, int* final_target,
+                          int* gen_target, void* stream) {
+  if (n_hosts != 16)
+    return fail(PGP_ERR_UNSUPPORTED, "fpe_forward1: n_hosts 16 only (FPE_16 with the fused Gen_16 / Disc_16)");
+  if (n_cells < 0) return fail(PGP_ERR_ARG, "fpe_forward1: negative n_cells");
+  if (n_protos < 1 || n_protos > kMaxProtos) return fail(PGP_ERR_ARG, "fpe_forward1: n_protos outside [1, 64]");
+  if (proto_stride < 2LL * n_protos) return fail(PGP_ERR_ARG, "fpe_forward1: proto_stride below 2 * n_protos");
+  if (n_cells == 0) return PGP_OK;
+  if (!windows || !h0 || !sched || !P_fpe || !P_master || !prototypes || !scores || !protos || !cls || !any_anom ||
+      !probs || !keep_orig || !final_target || !gen_target)
+    return fail(PGP_ERR_ARG, "fpe_forward1: NULL argument");
+  HIPCHK(launch_fpe_gate_cells(n_hosts, n_protos, n_cells, active, windows, h0, sched, P_fpe, P_master, prototypes,
+                               proto_stride, scores, protos, cls, any_anom, probs, keep_orig, final_target,
+                               gen_target, reinterpret_cast<hipStream_t>(stream)));
+  return PGP_OK;
+}
+
+int pgp_fpe_forward1(int n_hosts, int n_protos, const float* window, const float* h0, const float* sched,
+                     const float* P_fpe, const float* P_master, const double* prototypes_device, float* scores,
+                     float* protos, int* cls, int* any_anom, float* probs, int* keep_orig, int* final_target,
+                     int* gen_target, void* stream) {
+  return pgp_fpe_forward1_many(n_hosts, n_protos, 1, nullptr, window, h0, sched, P_fpe, P_master, prototypes_device,
+                               n_protos < 1 ? 2 : 2LL * n_protos, scores, protos, cls, any_anom, probs, keep_orig,
+                               final_target, gen_target, stream);
+}
+
 static const char* kGobiTrainHosts = "GOBI surrogate training: only energy_latency_16 exists (16 hosts)";
 
 int pgp_gobi_train_steps(int n_hosts, int n_samples, int n, const float* feats, const float* targets,

@@ -95,6 +95,14 @@ hipError_t launch_fpe_train_steps_cells(int n_hosts, int n_models, const pgp_fpe
 hipError_t launch_fpe_forward_cells(int n_hosts, int n_models, int max_n, const pgp_fpe_job* jobs_dev,
                                     const float* wins, const float* h0s, const float* P, double* probs,
                                     double* protos, hipStream_t st);
+// the gated forward (pgp_fpe1_cells.hip), 16 hosts: one workgroup per cell runs the FPE forward of window m under
+// slot m of P, then detect / embed / get_classes on row m of protos (proto_stride doubles apart) and Gen / Disc from
+// slot m of the training master; outputs as launch_fpe + K3 at batch 1 per cell.  active [n_cells] or nullptr.
+hipError_t launch_fpe_gate_cells(int n_hosts, int K, int n_cells, const int* active, const float* wins,
+                                 const float* h0s, const float* sched, const float* P, const float* master,
+                                 const double* protos, long long proto_stride, float* scores, float* protos_out,
+                                 int* cls, int* any_anom, float* probs, int* keep, int* final_t, int* gen_t,
+                                 hipStream_t st);
 
 // training of GOBI's surrogate (pgp_gobitrain.hip), 16 hosts: n sequential batch-1 Adam (L2) steps in
 // one launch / n independent per-sample losses.  hipErrorInvalidValue for any other H.

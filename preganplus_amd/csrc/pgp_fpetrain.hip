@@ -44,12 +44,19 @@
 // The kernel also has a cell-indexed form (template parameter CELLS, above the kernel): a
 // model's whole step loop with its AdamW in one workgroup, one workgroup per model of a fleet
 // (TRAIN), and the forwards of many models in one launch.
+//
+// GATE (pgp_fpe_forward1 / pgp_fpe_forward1_many, instantiated in pgp_fpe1_cells.hip): the
+// forward above for one window per cell, each cell on its own slot of P, continued in the same
+// workgroup by PreGANRecovery.run_model's rest of the interval's forward (PreGAN.py:105-126):
+// detect / embed / get_classes on the cell's prototypes and Gen_16 / Disc_16 on [emb; sched]
+// from the cell's training master (see FpeGateArgs).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
 #include "../../include/preganplus.h"
 #include "pgp_device.hpp"
+#include "pgp_gemm.hpp"
 #include "pgp_train.hpp"
 #include "pgp_tunetargets.hpp"
 
@@ -122,8 +129,33 @@ struct FpeCellArgs {
   int model0;               // forward: the launch's first model (models on grid y)
   AdamArgs adam;            // TRAIN: param / grad / m / v name slot 0, sched the pool's first row
 };
-template <bool CELLS>
-using FpeCell = std::conditional_t<CELLS, FpeCellArgs, int>;
+// GATE (pgp_fpe_forward1 / pgp_fpe_forward1_many): workgroup b is cell b.  The forward runs on
+// window b / h0 row b under slot b of P (FP<H>::SIZE floats apart), then, after its last barrier,
+//   detect / embed / get_classes (PreGAN.py:110-120) with K4's conventions: host h is anomalous iff
+//     an[h][1] > an[h][0], its embedding row is pr[h] where anomalous and zero otherwise, cls[h] the first
+//     argmin over the K prototypes (fp64, read as float) of the mean squared distance, -1 for a zero row;
+//   Gen_16 / Disc_16 on [emb; sched] from the gen / disc sections of slot b of the training master
+//     (TGeo<H>::ALL floats apart), infer1_kernel's arithmetic and lane mapping (pgp_tune1.hip) in four
+//     passes of 256 threads: 16 lanes per output of the two 64-output layers, 4 per output of Gen's
+//     second layer, DPP xor butterflies; the gate and both argmax targets.
+// The GAN part always runs, so every output is defined.  An inactive cell leaves before the first barrier.
+struct FpeGateArgs {
+  const int* active;     // [cells] or nullptr (all)
+  const float* sched;    // [cells][H][H]
+  const float* master;   // [cells][TGeo<H>::ALL]
+  const double* protos;  // [cells][proto_stride], the first 2K doubles of a row
+  long long proto_stride;
+  float* scores;         // [cells][H][2] anomaly softmax
+  float* protos_out;     // [cells][H][2]
+  int* cls;              // [cells][H]
+  int* any_anom;         // [cells]
+  float* probs;          // [cells][2]
+  int* keep;             // [cells]
+  int* final_t;          // [cells][H]
+  int* gen_t;            // [cells][H]
+};
+template <bool CELLS, bool GATE>
+using FpeCell = std::conditional_t<GATE, FpeGateArgs, std::conditional_t<CELLS, FpeCellArgs, int>>;
 template <bool LOOP>
 using FpeParam = std::conditional_t<LOOP, float*, const float* __restrict__>;
 template <bool LOOP>
@@ -131,13 +163,14 @@ using FpeGrad = std::conditional_t<LOOP, float*, float* __restrict__>;
 
 // The looped form at 16 hosts asks for two waves per SIMD (two workgroups per CU: 256 VGPRs, 7 of them spilled
 // in the prologue); at 50 hosts that spills inside the step, so it keeps one.  The other forms: as before.
-template <int H_, bool TRAIN, bool CELLS = false>
+template <int H_, bool TRAIN, bool CELLS = false, bool GATE = false>
 __global__ __launch_bounds__(kFT, TRAIN && CELLS && H_ <= 16 ? 2 : 1)
 void fpe_step_kernel(int K, const float* __restrict__ wins, const float* __restrict__ h0s,
                      const int* __restrict__ ys, const int* __restrict__ clss, FpeParam<TRAIN && CELLS> Pk,
                      FpeGrad<TRAIN && CELLS> Gk, double* __restrict__ state, double update_min, double decay,
                      double* __restrict__ loss, double* __restrict__ probs_out, double* __restrict__ protos_out,
-                     FpeCell<CELLS> cell) {
+                     FpeCell<CELLS, GATE> cell) {
+  static_assert(!GATE || (!TRAIN && !CELLS && H_ == 16), "the gated forward: 16 hosts, forward only");
   using C = FP<H_>;
   constexpr int H = C::H, W = C::W, E = C::E, D = C::D, L = C::L;
   constexpr bool kWide = H > 16;         // the 50-host forms
@@ -202,6 +235,10 @@ void fpe_step_kernel(int K, const float* __restrict__ wins, const float* __restr
       probs_out += j.step_off * (2 * H);
       protos_out += j.step_off * (2 * H);
     }
+  }
+  if constexpr (GATE) {  // the cell's slot; an inactive cell touches nothing
+    if (cell.active && !cell.active[blockIdx.x]) return;  // uniform over the workgroup, ahead of every barrier
+    slot = (long)blockIdx.x * C::SIZE;
   }
 [[maybe_unused]] next_step:  // TRAIN && CELLS: the job's following steps re-enter here, the row pointers moved on
   // P / G: the model's slot of the kernel's Pk / Gk (the lone forms: slot 0, Pk / Gk themselves).  The step loop
@@ -430,7 +467,114 @@ void fpe_step_kernel(int K, const float* __restrict__ wins, const float* __restr
     pr[t][1] = sigm(pr[t][1]);
   }
   __syncthreads();
-  if constexpr (!TRAIN) {
+  if constexpr (GATE) {
+    using TG = TGeo<H>;
+    constexpr int H2 = H * H, GIN = TG::GIN, DIN = TG::DIN;
+    static_assert(H <= kFT && 64 % (kFT / 16) == 0 && (4 * H2) % kFT == 0 && DIN % 16 == 0, "whole passes");
+    __shared__ float xin[GIN];  // Gen input [emb; s]
+    __shared__ float sd[DIN];   // Disc input [s; ns]
+    __shared__ float hg[64], hd[64];
+    __shared__ int anyf;
+    const long cb = blockIdx.x;
+    const float* __restrict__ sch = cell.sched + cb * H2;
+    const float* __restrict__ Gp = cell.master + cb * TG::ALL + TG::OFF_GEN;
+    const float* __restrict__ Dp = cell.master + cb * TG::ALL + TG::OFF_DISC;
+    const double* __restrict__ pk = cell.protos + cb * cell.proto_stride;
+    if (t == 0) anyf = 0;
+    __syncthreads();
+    if (t < 2 * H) {
+      cell.scores[cb * 2 * H + t] = an[t >> 1][t & 1];
+      cell.protos_out[cb * 2 * H + t] = pr[t >> 1][t & 1];
+    }
+    if (t < H) {  // detect + embed + get_classes
+      const float l0 = an[t][0], l1 = an[t][1];
+      const bool anom = l1 > l0;  // torch.argmax: ties -> index 0
+      const float e0 = anom ? pr[t][0] : 0.f, e1 = anom ? pr[t][1] : 0.f;
+      int cl = -1;
+      if (!(e0 == 0.f && e1 == 0.f)) {
+        float best = INFINITY;
+        for (int k = 0; k < K; ++k) {
+          const float d0 = e0 - (float)pk[2 * k], d1 = e1 - (float)pk[2 * k + 1];
+          const float dist = (d0 * d0 + d1 * d1) * 0.5f;  // torch.mean over PROTO_DIM = 2
+          if (dist < best) {                              // np.argmin: first minimum
+            best = dist;
+            cl = k;
+          }
+        }
+      }
+      cell.cls[cb * H + t] = cl;
+      xin[2 * t] = e0;
+      xin[2 * t + 1] = e1;
+      if (anom) anyf = 1;  // every writer stores 1
+    }
+    for (int i = t; i < H2; i += kFT) {
+      xin[2 * H + i] = sch[i];
+      sd[i] = sch[i];
+    }
+    __syncthreads();
+    // Gen1: 64 outputs, 16 lanes each (k-chunks), xor-butterfly sum; LeakyReLU(True) = identity
+    for (int o = t >> 4; o < 64; o += kFT / 16) {
+      const int sp = t & 15;
+      constexpr int KC = (GIN + 15) / 16;
+      float acc = 0.f;
+      for (int k = sp * KC; k < sp * KC + KC && k < GIN; ++k) acc = fmaf(Gp[TG::G_W1 + o * GIN + k], xin[k], acc);
+      acc = xadd<8>(xadd<4>(xadd<2>(xadd<1>(acc))));
+      if (sp == 0) hg[o] = acc + Gp[TG::G_B1 + o];
+    }
+    __syncthreads();
+    // Gen2: H^2 outputs, 4 lanes each: ns = s + 4 tanh(W2 hg + b2)
+    for (int i = t; i < 4 * H2; i += kFT) {
+      const int o = i >> 2, sp = i & 3;
+      float acc = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) acc = fmaf(Gp[TG::G_W2 + o * 64 + sp * 16 + k], hg[sp * 16 + k], acc);
+      acc = xadd<2>(xadd<1>(acc));
+      if (sp == 0) sd[H2 + o] = xin[2 * H + o] + 4.0f * tanhf(acc + Gp[TG::G_B2 + o]);
+    }
+    __syncthreads();
+    // Disc1: 64 outputs over [s; ns], 16 lanes each
+    for (int o = t >> 4; o < 64; o += kFT / 16) {
+      const int sp = t & 15;
+      constexpr int KC = DIN / 16;
+      float acc = 0.f;
+      for (int k = sp * KC; k < sp * KC + KC; ++k) acc = fmaf(Dp[TG::D_W1 + o * DIN + k], sd[k], acc);
+      acc = xadd<8>(xadd<4>(xadd<2>(xadd<1>(acc))));
+      if (sp == 0) hd[o] = acc + Dp[TG::D_B1 + o];
+    }
+    __syncthreads();
+    if (t < 64) {  // Disc2 + softmax + gate (PreGAN.py:74-76), one wave
+      float z0 = Dp[TG::D_W2 + ln] * hd[ln], z1 = Dp[TG::D_W2 + 64 + ln] * hd[ln];
+      z0 = pgp::wave_sum(z0);  // xor 32 .. 1 (pgp_gemm.hpp)
+      z1 = pgp::wave_sum(z1);
+      z0 += Dp[TG::D_B2];
+      z1 += Dp[TG::D_B2 + 1];
+      const float m = fmaxf(z0, z1), e0 = expf(z0 - m), e1 = expf(z1 - m), inv = 1.0f / (e0 + e1);
+      if (ln == 0) {
+        cell.probs[cb * 2] = e0 * inv;
+        cell.probs[cb * 2 + 1] = e1 * inv;
+        cell.keep[cb] = e0 * inv > e1 * inv ? 1 : 0;
+        cell.any_anom[cb] = anyf;
+      }
+    } else if (t < 64 + H) {  // first argmax of each schedule row (original / generated)
+      const int c2 = t - 64;
+      float bs = -INFINITY, bn = -INFINITY;
+      int is = 0, in = 0;
+      for (int h = 0; h < H; ++h) {
+        const float v = sd[c2 * H + h], w = sd[H2 + c2 * H + h];
+        if (v > bs) {
+          bs = v;
+          is = h;
+        }
+        if (w > bn) {
+          bn = w;
+          in = h;
+        }
+      }
+      cell.final_t[cb * H + c2] = is;
+      cell.gen_t[cb * H + c2] = in;
+    }
+    return;
+  } else if constexpr (!TRAIN) {
     if (t < 2 * H) {
       probs_out[(long)b * 2 * H + t] = (double)an[t >> 1][t & 1];
       protos_out[(long)b * 2 * H + t] = (double)pr[t >> 1][t & 1];
@@ -718,8 +862,26 @@ void fpe_step_kernel(int K, const float* __restrict__ wins, const float* __restr
 
 // The cell-indexed instantiations and their launches live in a translation unit of their own
 // (pgp_fpetrain_cells.hip includes this file with PGP_FPE_CELLS_TU), as pgp_gan1_cells.hip's: each
-// unit instantiates one family only, and the four lone kernels are built as before.
-#ifndef PGP_FPE_CELLS_TU
+// unit instantiates one family only, and the four lone kernels are built as before.  The gated
+// forward's likewise (pgp_fpe1_cells.hip, PGP_FPE_GATE_TU).
+#if defined(PGP_FPE_GATE_TU)
+
+// One workgroup per cell on grid x (no cap of its own); LDS is static.
+hipError_t launch_fpe_gate_cells(int n_hosts, int K, int n_cells, const int* active, const float* wins,
+                                 const float* h0s, const float* sched, const float* P, const float* master,
+                                 const double* protos, long long proto_stride, float* scores, float* protos_out,
+                                 int* cls, int* any_anom, float* probs, int* keep, int* final_t, int* gen_t,
+                                 hipStream_t st) {
+  if (n_hosts != 16) return hipErrorInvalidValue;
+  if (n_cells <= 0) return hipSuccess;
+  const FpeGateArgs g{active, sched,    master, protos, proto_stride, scores, protos_out,
+                      cls,    any_anom, probs,  keep,   final_t,      gen_t};
+  fpe_step_kernel<16, false, false, true><<<n_cells, kFT, 0, st>>>(K, wins, h0s, nullptr, nullptr, P, nullptr, nullptr,
+                                                                   0.0, 0.0, nullptr, nullptr, nullptr, g);
+  return hipGetLastError();
+}
+
+#elif !defined(PGP_FPE_CELLS_TU)
 
 int fpe_param_count(int H) { return H == 16 ? FP<16>::SIZE : H == 50 ? FP<50>::SIZE : 0; }
 

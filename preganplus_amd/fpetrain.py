@@ -62,6 +62,14 @@ def adam_table(tensors, positive, lr, b1, b2):
     return np.asarray(rows, dtype=np.float64).reshape(len(rows), len(tensors), 3).astype(np.float32)
 
 
+def fpe_blob(fpe: dict, H: int = 16) -> torch.Tensor:
+    """The natural fp32 parameter blob of an FPE weight dict, in state_dict order
+    (weights.fpe_shapes(H); pgp_fpe_param_len(H) floats), on the host: what
+    ``FPETrainer.P`` holds and ``pgp_fpe_forward1`` reads."""
+    blob = np.concatenate([np.asarray(fpe[k], dtype=np.float64).reshape(-1) for k in W.fpe_shapes(H)])
+    return torch.tensor(blob, dtype=torch.float32)
+
+
 class FPETrainer:
     """fp32 master weights, gradients and AdamW moments of the H-host FPE on the
     device, in state_dict order (weights.fpe_shapes(H)); H in SUPPORTED_H."""
@@ -82,9 +90,8 @@ class FPETrainer:
             self.tensors.append({"name": name, "shape": shp, "offset": off, "n": cnt, "step": 0.0})
             off += cnt
         assert off == n, (off, n)
-        blob = np.concatenate([np.asarray(fpe[k], dtype=np.float64).reshape(-1) for k in shapes])
         f32 = torch.float32
-        self.P = torch.tensor(blob, dtype=f32, device=self.device)
+        self.P = fpe_blob(fpe, H).to(self.device)
         self.G = torch.zeros_like(self.P)
         self.m = torch.zeros_like(self.P)
         self.v = torch.zeros_like(self.P)

@@ -42,10 +42,17 @@ generator, ``models.py:70``), so a seeded run reproduces the reference's h0.
 ``PreGANPlusFleetRecovery``: ``PreGANPlusRecovery.run_model``
 for M cells of 8 or 16 hosts at once, each on its own Transformer, Gen, Disc
 and prototypes (``train.FleetTuner``), each cell with the bits of a lone plugin.
+
+``PreGANFleetRecovery``: ``PreGANRecovery.run_model`` for M
+cells of 16 hosts at once, each on its own frozen FPE, prototypes, Gen and
+Disc: one detect launch (``pgp_fpe_forward1_many``), ``FleetTuner.train_gan``
+and one K5 call per interval, each cell with the bits of a lone
+``PreGANRecovery(..., master_forward=True)``.
 """
 from __future__ import annotations
 
 import atexit
+import ctypes
 import os
 import threading
 import warnings
@@ -54,6 +61,8 @@ import weakref
 import numpy as np
 import torch
 
+from . import _native
+from . import fpetrain as FT
 from . import train as TR
 from . import weights as W
 from .model import DecisionModel, FPEDecisionModel, assemble_decision, migrations, to_numpy
@@ -706,6 +715,64 @@ def _recover(env, hosts, schedule_data, original_decision, keep_original, device
 
 
 MODEL_FOLDER = "recovery/PreGANSrc/checkpoints"   # constants.py:2 (PreGAN's model_folder)
+MASTER_FORWARD_HOSTS = (16,)   # pgp_fpe_forward1: where the FPE kernels (16, 50) and the fused GAN kernels (8, 16) overlap
+
+
+def _gan_only(hosts, weights):
+    """A Trainer / FleetTuner weight dict that carries Gen / Disc alone: a zero Transformer beside them."""
+    return {"transformer": {k: np.zeros(s) for k, s in W.transformer_shapes(hosts).items()},
+            "gen": weights["gen"], "disc": weights["disc"], "prototypes": np.zeros((hosts, W.PROTO_DIM))}
+
+
+class _FpeForwardIO:
+    """Staging of ``pgp_fpe_forward1`` (M = 1) / ``pgp_fpe_forward1_many``: windows | h0 | sched |
+    active in one upload from pinned memory, one launch for all cells, every output in one download."""
+
+    def __init__(self, M, H, K, device):
+        self.M, self.H, self.K, self.device = M, H, K, device
+        self._L = _native.lib()
+        f32, i32 = np.float32, np.int32
+        lay, total = TR._aligned_layout([("windows", f32, (M, 3, 3 * H)), ("h0", f32, (M, 3)),
+                                         ("sched", f32, (M, H, H)), ("active", i32, (M,))])
+        self.hin = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self.din = torch.zeros(total, dtype=torch.uint8, device=device)
+        view = lambda buf, dt, shp, o, nb: buf[o:o + nb].view(TR._NP2TORCH[dt]).view(shp)
+        self.h = {name: view(self.hin, dt, shp, o, nb).numpy() for name, dt, shp, o, nb in lay}
+        self.d = {name: view(self.din, dt, shp, o, nb) for name, dt, shp, o, nb in lay}
+        lay, total = TR._aligned_layout([("scores", f32, (M, H, 2)), ("protos", f32, (M, H, 2)), ("cls", i32, (M, H)),
+                                         ("any", i32, (M,)), ("probs", f32, (M, 2)), ("keep", i32, (M,)),
+                                         ("final_target", i32, (M, H)), ("gen_target", i32, (M, H))])
+        self.dout = torch.zeros(total, dtype=torch.uint8, device=device)
+        self.hout = torch.zeros(total, dtype=torch.uint8).pin_memory()
+        self.out = {name: view(self.dout, dt, shp, o, nb) for name, dt, shp, o, nb in lay}
+        self.views = {name: view(self.hout, dt, shp, o, nb).numpy() for name, dt, shp, o, nb in lay}
+
+    def launch(self, P_fpe, P_master, protos, active=None, upload=True):
+        """Upload the staged inputs (``self.h``: windows / h0 / sched, filled by the caller) and launch;
+        ``upload=False``: the launch alone, on the inputs already on the device."""
+        M, H, K = self.M, self.H, self.K
+        if upload:
+            self.h["active"][...] = 1 if active is None else np.asarray(active, dtype=bool).reshape(M)
+            self.din.copy_(self.hin, non_blocking=True)
+        d, o = self.d, self.out
+        outs = [o[k].data_ptr() for k in ("scores", "protos", "cls", "any", "probs", "keep", "final_target",
+                                          "gen_target")]
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if M == 1 and active is None:
+            _native.check(self._L.pgp_fpe_forward1(
+                H, K, d["windows"].data_ptr(), d["h0"].data_ptr(), d["sched"].data_ptr(), P_fpe.data_ptr(),
+                P_master.data_ptr(), protos.data_ptr(), *outs, st), "pgp_fpe_forward1")
+        else:
+            _native.check(self._L.pgp_fpe_forward1_many(
+                H, K, M, d["active"].data_ptr(), d["windows"].data_ptr(), d["h0"].data_ptr(), d["sched"].data_ptr(),
+                P_fpe.data_ptr(), P_master.data_ptr(), protos.data_ptr(), 2 * K, *outs, st), "pgp_fpe_forward1_many")
+
+    def run(self, P_fpe, P_master, protos, active=None):
+        """``launch`` and ONE download: numpy views of the pinned copy (valid until the next call)."""
+        self.launch(P_fpe, P_master, protos, active)
+        self.hout.copy_(self.dout, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self.views
 
 
 class PreGANRecovery(_SaveGan, Recovery):
@@ -714,11 +781,21 @@ class PreGANRecovery(_SaveGan, Recovery):
     (save_gan, utils.py:86-88: Disc with epoch 0 and []) into the folder the
     models were loaded from, on the same writer thread as PreGANPlusRecovery;
     a plugin built from injected ``weights=`` (tests, benches) writes only when
-    ``save_folder`` is given."""
+    ``save_folder`` is given.
+
+    ``master_forward=True`` (16 hosts; off by default): ``run_encoder`` is one
+    ``pgp_fpe_forward1`` launch on the natural FPE blob and the training
+    master, the gate after ``train_gan`` is the fused step's own
+    (``Trainer.gan_probs_after``), and the host repack of the packed model
+    after every GAN step is skipped: the forward reads the master.  It is what
+    a cell of ``PreGANFleetRecovery`` equals bit for bit."""
 
     def __init__(self, hosts, env, training=False, device=None, model_folder=None, save_folder=_AUTO,
-                 weights=None, extra=None, init_seed=0):
+                 weights=None, extra=None, init_seed=0, master_forward=False):
         super().__init__()
+        self.master_forward = bool(master_forward)
+        if self.master_forward and hosts not in MASTER_FORWARD_HOSTS:
+            raise ValueError(f"master_forward runs pgp_fpe_forward1: hosts in {MASTER_FORWARD_HOSTS}, not {hosts}")
         self.init_seed = int(init_seed)   # seeds a fresh model's initialisation (no checkpoint, no packaged weights)
         self.model_name = f"FPE_{hosts}"
         self.gen_name = f"Gen_{hosts}"
@@ -770,10 +847,18 @@ class PreGANRecovery(_SaveGan, Recovery):
         self.accuracy_list = W.accuracy_list_from_arrays(self.extra, "meta/gen/accuracy_list")
         self.trainer = None
         if self.training:
-            gan_only = {"transformer": {k: np.zeros(s) for k, s in W.transformer_shapes(self.hosts).items()},
-                        "gen": weights["gen"], "disc": weights["disc"],
-                        "prototypes": np.zeros((self.hosts, W.PROTO_DIM))}
-            self.trainer = TR.Trainer(self.hosts, gan_only, self.extra, device=self.device)
+            self.trainer = TR.Trainer(self.hosts, _gan_only(self.hosts, weights), self.extra, device=self.device)
+        if self.master_forward:
+            dev = self.model.device
+            protos = np.ascontiguousarray(weights["prototypes"], dtype=np.float64)
+            self._fpe_P = FT.fpe_blob(weights["fpe"], self.hosts).to(dev)
+            self._protos_dev = torch.from_numpy(protos).to(dev)
+            self._master_P = None   # training: the trainer's own P, read at every call
+            if self.trainer is None:   # inference only: the master's bytes without a trainer's gradients and moments
+                n = int(_native.lib().pgp_master_len(self.hosts))
+                self._master_P = torch.tensor(W.pack_blob(_gan_only(self.hosts, weights), self.hosts)[:n],
+                                              dtype=torch.float32, device=dev)
+            self._fwd_io = _FpeForwardIO(1, self.hosts, protos.shape[0], dev)
         if "train_time_data" in self.extra:
             self.train_time_data = np.asarray(self.extra["train_time_data"], dtype=np.float64)
         else:
@@ -844,6 +929,11 @@ class PreGANRecovery(_SaveGan, Recovery):
             td = td[-3:]
         win = TR.convert_to_windows(td)[-1]
         h0 = torch.randn(1, 1, 3, dtype=torch.double)                     # models.py:70
+        if self.master_forward:
+            io = self._fwd_io
+            io.h["windows"][0], io.h["h0"][0], io.h["sched"][0] = win, h0.reshape(3).numpy(), schedule_data
+            master = self.trainer.P if self.trainer is not None else self._master_P
+            return io.run(self._fpe_P, master, self._protos_dev)
         dev = self.model.device
         f32 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32, device=dev).contiguous()
         return to_numpy(self.model.forward(f32(win[None]), f32(h0.reshape(1, 3)),
@@ -856,15 +946,18 @@ class PreGANRecovery(_SaveGan, Recovery):
         _, _, _, gen_loss, disc_loss = TR.train_gan(self.trainer, embedding, schedule_data, self._score)
         self.epoch += 1
         self.accuracy_list.append((gen_loss, disc_loss))                          # PreGAN.py:67
-        w = self.trainer.weights_numpy()
-        self.weights = dict(self.weights, gen=w["gen"], disc=w["disc"])
-        self.model.load_weights(self.weights)     # keep K3's packed GAN in step with the master
+        if not self.master_forward:                # (its forward reads the master itself)
+            w = self.trainer.weights_numpy()
+            self.weights = dict(self.weights, gen=w["gen"], disc=w["disc"])
+            self.model.load_weights(self.weights)     # keep K3's packed GAN in step with the master
         if self.save_gan:                          # save_gan (utils.py:86-88): Disc with epoch 0, []
             self._post_gan_checkpoint()
 
     # -- PreGAN.py:73-95 --
     def recover_decision(self, embedding, schedule_data, original_decision):
-        if self.trainer is not None:
+        if self.trainer is not None and self.master_forward:
+            p = self.trainer.gan_probs_after       # the fused step's last forward: the updated GAN's gate
+        elif self.trainer is not None:
             _, probs = self.trainer.gan_forward(np.asarray(embedding)[None], np.asarray(schedule_data)[None])
             p = probs[0].cpu().numpy()
         else:
@@ -1153,6 +1246,190 @@ class PreGANPlusFleetRecovery:
         tr, st = self.tuner.trainer(m)
         save_checkpoints(tr, folder, self.env_name, self.model_epoch[m], self.model_accuracy_list[m],
                          [("transformer", self.model_name, st.protos)])
+        save_checkpoints(tr, folder, self.env_name, self.epoch[m], self.accuracy_list[m],
+                         [("gen", self.gen_name, None)])
+        save_checkpoints(tr, folder, self.env_name, 0, [], [("disc", self.disc_name, None)])
+
+
+class PreGANFleetRecovery:
+    """``PreGANRecovery.run_model`` (PreGAN.py:105-126) for a fleet of M cells of
+    16 hosts (``MASTER_FORWARD_HOSTS``), each with its own frozen FPE_16,
+    prototypes, Gen_16, Disc_16 and GAN optimizer state — the reference keeps
+    one of each per PreGANRecovery.
+
+    weights / extras: per cell what ``PreGANRecovery(weights=, extra=)`` takes
+    (``fpe``, ``gen``, ``disc``, ``prototypes``; ``train_time_data``, the GAN's
+    optimizer state, ``meta/gen/*``).  The M natural FPE blobs
+    [M][pgp_fpe_param_len] (``fpetrain.fpe_blob``, what ``FPETrainer.P`` holds) and
+    the prototypes [M][K][2] fp64 stay on the device; Gen / Disc live in the
+    slots of a ``TR.FleetTuner`` built from zero-Transformer dicts, whose ``P``
+    the forward reads and whose ``train_gan`` is the GAN step.
+
+    ``setEnvironments(envs)`` as ``PreGANPlusFleetRecovery``;
+    ``run_model(original_decisions, h0=None)`` returns per cell what the lone
+    plugin's ``run_model`` returns.  One call: every cell's ``run_encoder``
+    window, GRU state and schedule in one upload, ONE ``pgp_fpe_forward1_many``
+    launch and one download; cells without an anomaly keep their decision and
+    are inactive from there on; with ``training`` the others take
+    ``FleetTuner.train_gan`` around their ``env.stats.runSimulation`` and are
+    gated by their updated GAN, otherwise by the forward's ``keep_orig``; all
+    deciding cells' decisions come from one K5 call.  ``h0`` [M,3]: the cells'
+    GRU states; None draws them per cell in cell order as the lone plugin draws
+    its own (``torch.randn(1, 1, 3, dtype=torch.double)``, models.py:70), so a
+    fleet of one draws what the lone plugin draws.  Each cell has the bits of a
+    lone ``PreGANRecovery(..., master_forward=True)`` given the same ``h0``.
+    Per cell ``accuracy_list``, ``epoch``, ``classes`` and ``hosts_from`` are
+    kept as the lone plugin keeps them.  The FPE is frozen (PreGAN.py:29):
+    nothing tunes it; ``set_fpe(m, fpe, prototypes)`` replaces cell m's, e.g.
+    by a model of ``fpetrain.train_fleet``.
+
+    ``save_checkpoints(folder, m)`` writes cell m's Gen / Disc checkpoints as
+    the lone plugin's ``save_gan`` does; the per-call asynchronous writer is
+    out of scope here and off."""
+
+    def __init__(self, hosts, weights, extras=None, training=False, device=None, env=""):
+        if hosts not in MASTER_FORWARD_HOSTS:
+            raise ValueError(f"the PreGAN fleet plugin runs pgp_fpe_forward1_many: hosts in {MASTER_FORWARD_HOSTS}, "
+                             f"not {hosts}")
+        weights = list(weights)
+        extras = [e or {} for e in (extras if extras is not None else [None] * len(weights))]
+        if len(weights) == 0:
+            raise ValueError("a fleet needs at least one cell")
+        if len(extras) != len(weights):
+            raise ValueError(f"extras: {len(extras)} entries for {len(weights)} cells")
+        Ks = {np.asarray(w["prototypes"]).shape[0] for w in weights}
+        if len(Ks) != 1:
+            raise ValueError(f"every cell needs the same number of prototypes, got {sorted(Ks)}")
+        self.hosts, self.training = hosts, training
+        self.K = Ks.pop()
+        self.env_name = "simulator" if env == "" else "framework"
+        self.model_name, self.gen_name, self.disc_name = f"FPE_{hosts}", f"Gen_{hosts}", f"Disc_{hosts}"
+        self.tuner = TR.FleetTuner(hosts, [_gan_only(hosts, w) for w in weights], extras, device=device)
+        self.M = M = self.tuner.M
+        self.device = dev = self.tuner.device
+        self.extras = extras
+        self.fpe_P = torch.stack([FT.fpe_blob(w["fpe"], hosts) for w in weights]).to(dev)
+        self.prototypes = torch.from_numpy(
+            np.stack([np.asarray(w["prototypes"], dtype=np.float64).reshape(self.K, W.PROTO_DIM)
+                      for w in weights])).to(dev)
+        self.epoch = [int(e.get("meta/gen/epoch", 0)) for e in extras]
+        self.accuracy_list = [W.accuracy_list_from_arrays(e, "meta/gen/accuracy_list") for e in extras]
+        self.train_time_data = []
+        for e in extras:
+            if "train_time_data" in e:
+                self.train_time_data.append(np.asarray(e["train_time_data"], dtype=np.float64))
+            else:
+                self.train_time_data.append(
+                    np.load(os.path.join("recovery/PreGANSrc/data", self.env_name, "time_series.npy")))
+        self.classes = [None] * M
+        self.hosts_from = [None] * M
+        self.envs = None
+        self._io = _FpeForwardIO(M, hosts, self.K, dev)
+        self._rio_many = None
+
+    def setEnvironments(self, envs):
+        envs = list(envs)
+        if len(envs) != self.M:
+            raise ValueError(f"{len(envs)} environments for {self.M} cells")
+        self.envs = envs
+
+    def set_fpe(self, m, fpe, prototypes):
+        """Replace cell m's frozen encoder and prototypes (an fp64 weight dict as
+        ``FPETrainer.weights_numpy`` returns it, prototypes [K,2])."""
+        if not 0 <= m < self.M:
+            raise ValueError(f"set_fpe: cell {m} outside [0, {self.M})")
+        p = np.asarray(prototypes, dtype=np.float64)
+        if p.shape != (self.K, W.PROTO_DIM):
+            raise ValueError(f"set_fpe: prototypes must be [{self.K},{W.PROTO_DIM}], not {p.shape}")
+        self.fpe_P[m].copy_(FT.fpe_blob(fpe, self.hosts))
+        self.prototypes[m].copy_(torch.from_numpy(np.ascontiguousarray(p)))
+
+    def _input_window(self, m):   # run_encoder, PreGAN.py:97-103
+        td = TR.normalize_test_time_data(self.envs[m].stats.time_series, self.train_time_data[m])
+        if td.shape[0] >= 3:
+            td = td[-3:]
+        return TR.convert_to_windows(td)[-1]
+
+    def _score(self, m):
+        def score(schedule):      # utils.py:97-100
+            e, r = self.envs[m].stats.runSimulation(torch.tensor(schedule))
+            return COEFF_ENERGY * e + COEFF_LATENCY * r
+        return score
+
+    def forward(self, windows, h0, scheds, active=None):
+        """The interval's forward of every (active) cell on its own FPE, prototypes and Gen / Disc: one
+        launch, one download -> ``FPEDecisionModel.forward``'s dict with batch M, numpy views of the pinned
+        copy (valid until the next call)."""
+        io = self._io
+        io.h["windows"][...] = np.asarray(windows).reshape(self.M, 3, 3 * self.hosts)
+        io.h["h0"][...] = np.asarray(h0).reshape(self.M, 3)
+        io.h["sched"][...] = np.asarray(scheds).reshape(self.M, self.hosts, self.hosts)
+        return io.run(self.fpe_P, self.tuner.P, self.prototypes, active)
+
+    def run_model(self, original_decisions, h0=None):
+        M, H = self.M, self.hosts
+        original_decisions = list(original_decisions)
+        if self.envs is None or len(original_decisions) != M:
+            raise ValueError(f"run_model: setEnvironments first, and one original decision per cell ({M})")
+        scheds = np.stack([np.asarray(e.scheduler.result_cache, dtype=np.float64) for e in self.envs])
+        wins = np.stack([self._input_window(m) for m in range(M)])
+        if h0 is None:            # models.py:70, per cell in cell order
+            h0 = np.stack([torch.randn(1, 1, 3, dtype=torch.double).numpy().reshape(3) for _ in range(M)])
+        elif np.asarray(h0).shape != (M, 3):
+            raise ValueError(f"run_model: h0 must be [{M},3], not {np.asarray(h0).shape}")
+        out = self.forward(wins, h0, scheds)
+        act = out["any"].astype(bool).copy()
+        res = list(original_decisions)       # no anomaly: the original decision (PreGAN.py:112-114)
+        if not act.any():
+            return res
+        cells = np.flatnonzero(act)
+        anom = out["scores"][:, :, 1] > out["scores"][:, :, 0]
+        emb = np.where(anom[:, :, None], out["protos"], 0.0).astype(np.float32)
+        for m in cells:
+            self.classes[m] = out["cls"][m].tolist()
+        if self.training:
+            gan = self.tuner.train_gan(emb, scheds, simulate=[self._score(m) for m in range(M)], active=act)
+            for m in cells:                  # PreGAN.py:66-67
+                self.epoch[m] += 1
+                self.accuracy_list[m].append((gan[m][3], gan[m][4]))
+            p = self.tuner.gan_probs_after
+            keep = p[:, 0] > p[:, 1]         # each cell's own updated gate (PreGAN.py:74-76)
+        else:
+            keep = out["keep"].astype(bool)
+        self._recover_many(cells, keep, res, original_decisions, out["final_target"])
+        return res
+
+    def _recover_many(self, cells, keep, res, original_decisions, final_target):
+        """``_recover`` (PreGAN.py:77-95) for every deciding cell in one K5 call at batch M; inactive
+        and keeping cells are staged as keep = 1 and their rows ignored."""
+        M, H = self.M, self.hosts
+        if self._rio_many is None:
+            self._rio_many = _RecoverManyIO(M, H, self.device)
+        io = self._rio_many
+        io.keep[:] = 1
+        io.cur[:] = -1
+        io.final_target[...] = final_target
+        deciding = []
+        for m in cells:
+            if keep[m]:                      # the original decision stands (PreGAN.py:75-76)
+                res[m] = original_decisions[m]
+                continue
+            io.keep[m] = 0
+            cur = io.cur[m]
+            for c in self.envs[m].containerlist:
+                if c and c.getHostID() != -1:
+                    cur[c.id] = c.getHostID()
+            deciding.append(m)
+        if not deciding:
+            return
+        moves, hosts_from = io.run()
+        for m in deciding:
+            res[m] = assemble_decision(original_decisions[m], moves[m], io.cur[m])
+            self.hosts_from[m] = hosts_from[m].tolist()
+
+    # -- save_gan per cell (utils.py:86-88: Disc with epoch 0 and []) --
+    def save_checkpoints(self, folder, m):
+        tr, _ = self.tuner.trainer(m)
         save_checkpoints(tr, folder, self.env_name, self.epoch[m], self.accuracy_list[m],
                          [("gen", self.gen_name, None)])
         save_checkpoints(tr, folder, self.env_name, 0, [], [("disc", self.disc_name, None)])
