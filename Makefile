@@ -4,11 +4,11 @@ ARCH ?= gfx950
 LIBDIR := preganplus_amd/_lib
 LIB := $(LIBDIR)/libpreganplus.so
 CSRC := preganplus_amd/csrc
-KSRCS := $(CSRC)/pgp_tunef.hip $(CSRC)/pgp_dec.hip $(CSRC)/pgp_gat.hip $(CSRC)/pgp_encoder.hip $(CSRC)/pgp_decoder.hip $(CSRC)/pgp_gan.hip $(CSRC)/pgp_gansplit.hip $(CSRC)/pgp_train.hip $(CSRC)/pgp_tune.hip $(CSRC)/pgp_tune1.hip $(CSRC)/pgp_tune1_cells.hip $(CSRC)/pgp_gan1.hip $(CSRC)/pgp_gan1_cells.hip $(CSRC)/pgp_tunedp.hip $(CSRC)/pgp_tunescore.hip $(CSRC)/pgp_tunedata_cells.hip $(CSRC)/pgp_gantrain.hip $(CSRC)/pgp_gobi.hip $(CSRC)/pgp_gobitrain.hip $(CSRC)/pgp_sim.hip $(CSRC)/pgp_fpe.hip $(CSRC)/pgp_fpetrain.hip $(CSRC)/pgp_fpetrain_cells.hip $(CSRC)/pgp_fpe1_cells.hip $(CSRC)/pgp_decide.hip $(CSRC)/pgp_repack.hip $(CSRC)/pgp_online.hip $(CSRC)/pgp_capi.hip
+KSRCS := $(CSRC)/pgp_tunef.hip $(CSRC)/pgp_dec.hip $(CSRC)/pgp_gat.hip $(CSRC)/pgp_encoder.hip $(CSRC)/pgp_decoder.hip $(CSRC)/pgp_gan.hip $(CSRC)/pgp_gansplit.hip $(CSRC)/pgp_train.hip $(CSRC)/pgp_tune.hip $(CSRC)/pgp_tune1.hip $(CSRC)/pgp_tune1_cells.hip $(CSRC)/pgp_gan1.hip $(CSRC)/pgp_gan1_cells.hip $(CSRC)/pgp_tunedp.hip $(CSRC)/pgp_tunescore.hip $(CSRC)/pgp_tunedata_cells.hip $(CSRC)/pgp_gantrain.hip $(CSRC)/pgp_gobi.hip $(CSRC)/pgp_gobi_so.hip $(CSRC)/pgp_gobitrain.hip $(CSRC)/pgp_sim.hip $(CSRC)/pgp_fpe.hip $(CSRC)/pgp_fpetrain.hip $(CSRC)/pgp_fpetrain_cells.hip $(CSRC)/pgp_fpe1_cells.hip $(CSRC)/pgp_decide.hip $(CSRC)/pgp_repack.hip $(CSRC)/pgp_online.hip $(CSRC)/pgp_capi.hip
 SRCS := $(KSRCS) $(CSRC)/pgp_pack.cpp
 OBJDIR := build/obj
 OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(SRCS))
-HDRS := include/preganplus.h $(CSRC)/pgp_tunef.hpp $(CSRC)/pgp_layout.hpp $(CSRC)/pgp_pack.hpp $(CSRC)/pgp_device.hpp $(CSRC)/pgp_train.hpp $(CSRC)/pgp_tune.hpp $(CSRC)/pgp_tunedp.hpp $(CSRC)/pgp_tunescore.hpp $(CSRC)/pgp_tunedata_cells.hpp $(CSRC)/pgp_tunetargets.hpp $(CSRC)/pgp_gemm.hpp $(CSRC)/pgp_packcore.hpp $(CSRC)/pgp_repack.hpp $(CSRC)/pgp_philox.hpp $(CSRC)/pgp_encoder_body.inc $(CSRC)/pgp_tune1.hip $(CSRC)/pgp_gan1.hip $(CSRC)/pgp_fpetrain.hip
+HDRS := include/preganplus.h $(CSRC)/pgp_tunef.hpp $(CSRC)/pgp_layout.hpp $(CSRC)/pgp_pack.hpp $(CSRC)/pgp_device.hpp $(CSRC)/pgp_train.hpp $(CSRC)/pgp_tune.hpp $(CSRC)/pgp_tunedp.hpp $(CSRC)/pgp_tunescore.hpp $(CSRC)/pgp_tunedata_cells.hpp $(CSRC)/pgp_tunetargets.hpp $(CSRC)/pgp_gemm.hpp $(CSRC)/pgp_packcore.hpp $(CSRC)/pgp_repack.hpp $(CSRC)/pgp_philox.hpp $(CSRC)/pgp_gobi.hpp $(CSRC)/pgp_encoder_body.inc $(CSRC)/pgp_tune1.hip $(CSRC)/pgp_gan1.hip $(CSRC)/pgp_fpetrain.hip
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 
 .PHONY: all clean resource-usage variant asan

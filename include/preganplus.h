@@ -49,6 +49,10 @@
  *       a fleet whose environments have their own surrogates (one dataset and
  *       checkpoint per environment, scheduler/GOBI.py:11-17): M trained in one
  *       launch, each environment optimised against its own
+ *   pgp_gobi_so_optimize / pgp_gobi_so_optimize_groups
+ *       second-order GOBI: SOGOBIScheduler.run_SOGOBI's so_opt()
+ *       (scheduler/SOGOBI.py:18-40, scheduler/BaGTI/src/opt.py:35-51,
+ *       scheduler/BaGTI/src/adahessian.py:49-168)
  *   pgp_sim_env_len / pgp_simulate
  *       the GAN label: run_simulation (PreGANSrc/src/utils.py:97-100) ->
  *       Stats.runSimulation (stats/Stats.py:154-177), PreGANPlus.py:65-66
@@ -1051,6 +1055,45 @@ int pgp_gobi_optimize_groups(pgp_gobi* g, int n_env, int n_groups, const int* gr
                              float* result, int* iterations, float* fitness, int max_iters, float* pre,
                              void* stream);
 int pgp_gobi_plan_groups(int n_env, const int* model_of_env, int n_models, int* groups_out, int cap);
+
+/* ---- second-order GOBI (SOGOBI) ----
+ * pgp_gobi_so_optimize: so_opt() (scheduler/BaGTI/src/opt.py:35-51) with
+ *   Adahessian (scheduler/BaGTI/src/adahessian.py:49-168; lr 0.8, betas 0.9 /
+ *   0.999, eps 1e-4, hessian_power 1, no weight decay) under
+ *   CosineAnnealingLR(T_max=10), as SOGOBIScheduler.run_SOGOBI calls it
+ *   (scheduler/SOGOBI.py:18-40), of n_env independent environments on the
+ *   handle's model 0.  init / result / iterations / fitness / max_iters: as
+ *   pgp_gobi_optimize's (16 hosts; device arrays).  Each step draws one probe
+ *   v = +-1 per input entry (all 288, the cpu / ips columns included) for
+ *   hv = H v; an environment's probes depend on that environment alone:
+ *     signs != NULL: explicit, device uint32 [n_env][sign_steps][9]; bit k
+ *       (row-major entry k = c * 18 + f) of word k >> 5 set means +1.
+ *       sign_steps must reach the step limit (max_iters, or 200 for <= 0).
+ *     seeds != NULL: generated, device uint64 [n_env]; step s's word w is
+ *       output word 0 of Philox4x32-10 with key = seeds[e] (low, high) and
+ *       counter = (w, s, 0, 0); bit set means +1.  sign_steps is ignored.
+ *   Exactly one of the two.  taps: NULL, or device fp32 [n_env][3][16][18], a
+ *   test hook: the last executed step's g, hv and pre-projection x (the cpu /
+ *   ips columns of the third plane hold the value the projection restores,
+ *   their update being discarded).  An environment's outputs have the same
+ *   bits whatever the batch size and its position in it.
+ * pgp_gobi_so_optimize_groups: the same of each environment against its own
+ *   surrogate, over pgp_gobi_plan_groups's table ([n_groups][5]); a row's four
+ *   slots run as two workgroups.  Array shapes, the caller's order and the
+ *   inert-slot rules are pgp_gobi_optimize_groups's, signs / seeds / taps are
+ *   indexed by environment id, and an environment has the bits
+ *   pgp_gobi_so_optimize gives it on a handle of its model alone.
+ * Both return before anything is enqueued: PGP_ERR_UNSUPPORTED for a handle
+ * of another host count; PGP_ERR_ARG for a NULL handle, a negative count, a
+ * NULL array, both or neither of signs / seeds, or sign_steps below the step
+ * limit; PGP_OK for n_env == 0 (and n_groups == 0). */
+int pgp_gobi_so_optimize(pgp_gobi* g, int n_env, const float* init, float* result, int* iterations, float* fitness,
+                         int max_iters, const unsigned int* signs, int sign_steps, const unsigned long long* seeds,
+                         float* taps, void* stream);
+int pgp_gobi_so_optimize_groups(pgp_gobi* g, int n_env, int n_groups, const int* groups, const float* init,
+                                float* result, int* iterations, float* fitness, int max_iters,
+                                const unsigned int* signs, int sign_steps, const unsigned long long* seeds,
+                                float* taps, void* stream);
 
 /* ---- GAN-label simulation ----
  * Replaces the two env.stats.runSimulation calls of train_gan

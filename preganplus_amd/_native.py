@@ -174,6 +174,8 @@ SIGNATURES = {
     "pgp_gobi_set_model": (i32, [vp, i32, vp, sz]),
     "pgp_gobi_optimize_groups": (i32, [vp, i32, i32] + [vp] * 5 + [i32, vp, stream]),
     "pgp_gobi_plan_groups": (i32, [i32, vp, i32, vp, i32]),
+    "pgp_gobi_so_optimize": (i32, [vp, i32] + [vp] * 4 + [i32, vp, i32, vp, vp, stream]),
+    "pgp_gobi_so_optimize_groups": (i32, [vp, i32, i32] + [vp] * 5 + [i32, vp, i32, vp, vp, stream]),
     "pgp_sim_env_len": (sz, [i32]),
     "pgp_simulate": (i32, [i32, i32] + [vp] * 5 + [stream]),
 }

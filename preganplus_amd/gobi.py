@@ -46,6 +46,54 @@ def check_model_of(model_of, n_env, n_models) -> np.ndarray:
     return np.ascontiguousarray(mo, dtype=np.int32)
 
 
+def pack_signs(v) -> np.ndarray:
+    """Probes [..., 16, 18] of +-1 -> uint32 [..., 9]: bit k (row-major entry
+    k = c * 18 + f) of word k >> 5 set means +1 (pgp_gobi_so_optimize's signs)."""
+    v = np.asarray(v)
+    bits = (v.reshape(*v.shape[:-2], 9, 32) > 0).astype(np.uint64)
+    return (bits << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+def unpack_signs(words) -> np.ndarray:
+    """uint32 [..., 9] -> float32 [..., 16, 18] of +-1 (pack_signs' inverse)."""
+    w = np.asarray(words, dtype=np.uint32)
+    bits = (w[..., None] >> np.arange(32, dtype=np.uint32)) & 1
+    return (2.0 * bits.reshape(*w.shape[:-1], H, H + 2) - 1.0).astype(np.float32)
+
+
+def _philox4x32_10_word0(c0, c1, k0, k1) -> np.ndarray:
+    """Output word 0 of Philox4x32-10 (Salmon et al., SC'11; csrc/pgp_philox.hpp)
+    for counters (c0, c1, 0, 0) and keys (k0, k1): uint32 arrays, broadcast."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1, k0, k1 = (np.asarray(a, dtype=np.uint64) for a in np.broadcast_arrays(c0, c1, k0, k1))
+    c2 = np.zeros_like(c0)
+    c3 = np.zeros_like(c0)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c0.astype(np.uint32)
+
+
+def _seeds_u64(seeds) -> np.ndarray:
+    """Integer seeds (any signedness, Python ints up to 2^64 - 1) as uint64 [E]."""
+    if isinstance(seeds, torch.Tensor):
+        seeds = seeds.cpu().numpy()
+    if isinstance(seeds, np.ndarray) and np.issubdtype(seeds.dtype, np.integer):
+        return np.ascontiguousarray(seeds.astype(np.uint64).reshape(-1))
+    return np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
+
+
+def so_signs(seeds, steps) -> np.ndarray:
+    """The probes pgp_gobi_so_optimize generates from seeds [E], as its explicit
+    signs: uint32 [E, steps, 9], word w of step s = output word 0 of
+    Philox4x32-10 with key seeds[e] (low, high word) and counter (w, s, 0, 0)."""
+    s = _seeds_u64(seeds).reshape(-1, 1, 1)
+    step = np.arange(int(steps), dtype=np.uint64).reshape(1, -1, 1)
+    word = np.arange(9, dtype=np.uint64).reshape(1, 1, -1)
+    return _philox4x32_10_word0(word, step, s & np.uint64(0xFFFFFFFF), s >> np.uint64(32))
+
+
 class GOBIOptimizer:
     """Batched opt(): init [E,16,18] -> (result [E,16,18], iterations [E], fitness [E]).
 
@@ -160,6 +208,72 @@ class GOBIOptimizer:
             raise RuntimeError(f"pgp_gobi_optimize: {rc} {self._L.pgp_gobi_last_error().decode()}")
         return res, its, fit
 
+    def optimize_so(self, init, out=None, stream=None, max_iters=0, signs=None, seeds=None, taps=None, model_of=None,
+                    groups=None):
+        """Batched so_opt() (scheduler/BaGTI/src/opt.py:35-51, Adahessian:
+        scheduler/BaGTI/src/adahessian.py:49-168): optimize()'s shapes, result
+        and model_of / groups.  Each step probes the Hessian with one +-1 per
+        input entry; exactly one of
+          signs: uint32 [E, steps, 9] (pack_signs; steps >= the step limit),
+          seeds: integer [E] (a 64-bit device tensor is used where it is),
+                 environment e's probes are so_signs(seeds[e:e+1], steps).
+        max_iters / taps [E,3,16,18] (the last executed step's g, hv and
+        pre-projection x): test hooks."""
+        x = torch.as_tensor(init, dtype=torch.float32).to(self.device).contiguous()
+        if x.dim() != 3 or tuple(x.shape[1:]) != (H, H + 2):
+            raise ValueError(f"init must be [E,{H},{H + 2}], got {tuple(x.shape)}")
+        E = x.shape[0]
+        if (signs is None) == (seeds is None):
+            raise ValueError("signs (explicit probes) or seeds (generated), not both")
+        sign_steps = 0
+        if signs is not None:
+            if isinstance(signs, np.ndarray):
+                signs = torch.as_tensor(signs.view(np.int32))
+            signs = signs.to(self.device).contiguous()
+            if signs.dim() != 3 or signs.shape[0] != E or signs.shape[2] != 9 or signs.element_size() != 4:
+                raise ValueError(f"signs must be 32-bit words [{E}, steps, 9], got {tuple(signs.shape)}")
+            sign_steps = int(signs.shape[1])
+        else:
+            if isinstance(seeds, torch.Tensor) and seeds.is_cuda:   # device-resident seeds: used where they are
+                if seeds.dtype not in (torch.int64, torch.uint64) or tuple(seeds.shape) != (E,):
+                    raise ValueError(f"seeds must be {E} 64-bit integers, got {seeds.dtype} {tuple(seeds.shape)}")
+                seeds = seeds.to(self.device).contiguous()
+            else:
+                seeds = _seeds_u64(seeds)
+                if seeds.shape != (E,):
+                    raise ValueError(f"seeds must be {E} integers, got {seeds.shape[0]}")
+                seeds = torch.as_tensor(seeds.view(np.int64)).to(self.device)
+        if taps is not None and (taps.dtype != torch.float32 or tuple(taps.shape) != (E, 3, H, H + 2)
+                                 or not taps.is_cuda or not taps.is_contiguous()):
+            raise ValueError(f"taps must be a contiguous device float32 tensor [{E},3,{H},{H + 2}]")
+        if out is None:
+            out = (torch.empty_like(x), torch.empty(E, dtype=torch.int32, device=self.device),
+                   torch.empty(E, dtype=torch.float32, device=self.device))
+        res, its, fit = out
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if model_of is not None and groups is not None:
+            raise ValueError("model_of or groups, not both")
+        tail = (int(max_iters), None if signs is None else signs.data_ptr(), sign_steps,
+                None if seeds is None else seeds.data_ptr(), None if taps is None else taps.data_ptr(),
+                ctypes.c_void_p(st.cuda_stream))
+        if model_of is not None or groups is not None:
+            if groups is None:
+                groups, g = self.plan(model_of, E)
+            else:
+                if groups.dtype != torch.int32 or groups.dim() != 2 or groups.shape[1] != 5 or not groups.is_cuda:
+                    raise ValueError("groups must be a device int32 tensor [G,5]")
+                groups, g = groups.contiguous(), int(groups.shape[0])
+            rc = self._L.pgp_gobi_so_optimize_groups(self._h, E, g, groups.data_ptr(), x.data_ptr(), res.data_ptr(),
+                                                     its.data_ptr(), fit.data_ptr(), *tail)
+            what = "pgp_gobi_so_optimize_groups"
+        else:
+            rc = self._L.pgp_gobi_so_optimize(self._h, E, x.data_ptr(), res.data_ptr(), its.data_ptr(),
+                                              fit.data_ptr(), *tail)
+            what = "pgp_gobi_so_optimize"
+        if rc != 0:
+            raise RuntimeError(f"{what}: {rc} {self._L.pgp_gobi_last_error().decode()}")
+        return res, its, fit
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._L.pgp_gobi_destroy(self._h)
@@ -247,9 +361,12 @@ class GOBIScheduler(Scheduler):
             alloc.append(one)
         return np.concatenate((cpu, cpuc, np.array(alloc)), axis=1), prev
 
+    def _optimize(self, init):
+        return self.opt.optimize(init)
+
     def run_GOBI(self):
         init, prev = self.init_matrix()
-        res, _, _ = self.opt.optimize(init[None])
+        res, _, _ = self._optimize(init[None])
         result = res[0].cpu().numpy()
         self.result_cache = result[:, -self.hosts:]
         decision = []
@@ -262,3 +379,29 @@ class GOBIScheduler(Scheduler):
 
     def placement(self, containerIDs):
         return self.run_GOBI()
+
+
+class SOGOBIScheduler(GOBIScheduler):
+    """scheduler/SOGOBI.py:8-48: GOBIScheduler with the second-order optimiser
+    (run_SOGOBI's so_opt, SOGOBI.py:34).  run_GOBI, result_cache and the
+    decision list are GOBIScheduler's.  The reference draws its Hutchinson
+    probes from torch's global generator; here call n (from 0) of a scheduler
+    built with ``seed`` draws them from the per-call seed ``call_seed(n)``, so
+    a run is reproducible and two schedulers with different seeds are
+    independent."""
+
+    def __init__(self, data_type="energy_latency_16", device="cuda", weights=None, max_ips=None, seed=0):
+        super().__init__(data_type, device=device, weights=weights, max_ips=max_ips)
+        self.seed = int(seed)
+        self.calls = 0
+
+    def call_seed(self, n):
+        """The 64-bit probe seed of call n: the scheduler's seed in the high word, the call in the low."""
+        return ((self.seed & 0xFFFFFFFF) << 32) | (int(n) & 0xFFFFFFFF)
+
+    def _optimize(self, init):
+        seeds = np.array([self.call_seed(self.calls)], dtype=np.uint64)
+        self.calls += 1
+        return self.opt.optimize_so(init, seeds=seeds)
+
+    run_SOGOBI = GOBIScheduler.run_GOBI
