@@ -470,8 +470,34 @@ int pgp_fpe_forward_many(int n_hosts, int n, const float* windows, const float* 
   return PGP_OK;
 }
 
-static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float lr, float wd, double b1, double b2,
-                      float eps, const pgp_adam_tensor* t, int n, const float* sched, long lo, long hi);
+// The one place an AdamArgs is filled, from checked pointers and 0 <= n <= kMaxTensors.  sched == nullptr: every
+// tensor's (active, step_size, bc2_sqrt) are its descriptor's own; otherwise they come from the table's rows
+// (kAdamFromTable).  With lo <= hi every tensor must lie inside floats [lo, hi) of the buffers: false if one does not.
+static bool adam_args(AdamArgs* a, float* P, const float* G, float* m, float* v, float lr, float wd, double b1,
+                      double b2, float eps, const pgp_adam_tensor* t, int n, const float* sched, long lo = 0,
+                      long hi = -1) {
+  *a = AdamArgs{};
+  a->param = P;
+  a->grad = const_cast<float*>(G);
+  a->m = m;
+  a->v = v;
+  a->lr_wd = lr * wd;
+  a->b2 = (float)b2;
+  a->omb1 = adam_moment_weight(b1);
+  a->omb2 = adam_moment_weight(b2);
+  a->eps = eps;
+  a->ntensors = n;
+  a->sched = sched;
+  for (int i = 0; i < n; ++i) {
+    if (lo <= hi && (t[i].offset < lo || t[i].n < 0 || (long)t[i].offset + t[i].n > hi)) return false;
+    a->t[i].off = (long)t[i].offset;
+    a->t[i].n = t[i].n;
+    a->t[i].active = sched ? kAdamFromTable : t[i].active;
+    a->t[i].step_size = sched ? 0.f : t[i].step_size;
+    a->t[i].bc2_sqrt = sched ? 0.f : t[i].bc2_sqrt;
+  }
+  return true;
+}
 
 namespace {
 // what the three cell-indexed FPE entries check of their scalars and of the whole job table, before
@@ -998,30 +1024,6 @@ int pgp_gan_forward1(int n_hosts, const float* emb, const float* sched, const fl
   return PGP_OK;
 }
 
-static bool adam_args(AdamArgs* a, float* P, float* G, float* m, float* v, float lr, float wd, double b1, double b2,
-                      float eps, const pgp_adam_tensor* t, int n, const float* sched, long lo, long hi) {
-  if (!t || !sched || n < 0 || n > kMaxTensors) return false;
-  *a = AdamArgs{};
-  a->param = P;
-  a->grad = G;
-  a->m = m;
-  a->v = v;
-  a->lr_wd = lr * wd;
-  a->b2 = (float)b2;
-  a->omb1 = adam_moment_weight(b1);
-  a->omb2 = adam_moment_weight(b2);
-  a->eps = eps;
-  a->ntensors = n;
-  a->sched = sched;
-  for (int i = 0; i < n; ++i) {
-    if (t[i].offset < lo || t[i].n < 0 || (long)t[i].offset + t[i].n > hi) return false;  // inside the section
-    a->t[i].off = (long)t[i].offset;
-    a->t[i].n = t[i].n;
-    a->t[i].active = 1;
-  }
-  return true;
-}
-
 int pgp_gan_step1_d(int n_hosts, const float* target, float* P, float* G, float* exp_avg, float* exp_avg_sq,
                   float lr_disc, float lr_gen, float weight_decay, double beta1, double beta2, float eps,
                   const pgp_adam_tensor* disc_tensors, int n_disc, const float* disc_sched,
@@ -1033,7 +1035,9 @@ int pgp_gan_step1_d(int n_hosts, const float* target, float* P, float* G, float*
   if (!target || !P || !G || !exp_avg || !exp_avg_sq || !workspace || !probs_gen || !probs_after)
     return fail(PGP_ERR_ARG, "bad gan_step1 arguments");
   AdamArgs ad, ag;
-  if (!adam_args(&ad, P, G, exp_avg, exp_avg_sq, lr_disc, weight_decay, beta1, beta2, eps, disc_tensors, n_disc,
+  if (!disc_tensors || !disc_sched || n_disc < 0 || n_disc > kMaxTensors || !gen_tensors || !gen_sched || n_gen < 0 ||
+      n_gen > kMaxTensors ||
+      !adam_args(&ad, P, G, exp_avg, exp_avg_sq, lr_disc, weight_decay, beta1, beta2, eps, disc_tensors, n_disc,
                  disc_sched, dof, all) ||
       !adam_args(&ag, P, G, exp_avg, exp_avg_sq, lr_gen, weight_decay, beta1, beta2, eps, gen_tensors, n_gen,
                  gen_sched, go, dof))
@@ -1102,24 +1106,8 @@ int pgp_adamw_d(float* P, const float* G, float* exp_avg, float* exp_avg_sq, flo
   if (!P || !G || !exp_avg || !exp_avg_sq || !tensors || ntensors < 0 || ntensors > kMaxTensors)
     return fail(PGP_ERR_ARG, "bad adamw arguments");
   if (ntensors == 0) return PGP_OK;
-  AdamArgs a{};
-  a.param = P;
-  a.grad = const_cast<float*>(G);
-  a.m = exp_avg;
-  a.v = exp_avg_sq;
-  a.lr_wd = lr * weight_decay;
-  a.b2 = (float)beta2;
-  a.omb1 = adam_moment_weight(beta1);
-  a.omb2 = adam_moment_weight(beta2);
-  a.eps = eps;
-  a.ntensors = ntensors;
-  for (int i = 0; i < ntensors; ++i) {
-    a.t[i].off = (long)tensors[i].offset;
-    a.t[i].n = tensors[i].n;
-    a.t[i].active = tensors[i].active;
-    a.t[i].step_size = tensors[i].step_size;
-    a.t[i].bc2_sqrt = tensors[i].bc2_sqrt;
-  }
+  AdamArgs a;
+  adam_args(&a, P, G, exp_avg, exp_avg_sq, lr, weight_decay, beta1, beta2, eps, tensors, ntensors, nullptr);
   HIPCHK(launch_adamw(a, reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;
 }
@@ -1130,25 +1118,8 @@ int pgp_adamw_table_d(float* P, const float* G, float* exp_avg, float* exp_avg_s
   if (!P || !G || !exp_avg || !exp_avg_sq || !tensors || !sched || ntensors < 0 || ntensors > kMaxTensors)
     return fail(PGP_ERR_ARG, "bad adamw arguments");
   if (ntensors == 0) return PGP_OK;
-  AdamArgs a{};
-  a.param = P;
-  a.grad = const_cast<float*>(G);
-  a.m = exp_avg;
-  a.v = exp_avg_sq;
-  a.lr_wd = lr * weight_decay;
-  a.b2 = (float)beta2;
-  a.omb1 = adam_moment_weight(beta1);
-  a.omb2 = adam_moment_weight(beta2);
-  a.eps = eps;
-  a.ntensors = ntensors;
-  a.sched = sched;
-  for (int i = 0; i < ntensors; ++i) {
-    a.t[i].off = (long)tensors[i].offset;
-    a.t[i].n = tensors[i].n;
-    a.t[i].active = kAdamFromTable;  // every row from the table
-    a.t[i].step_size = tensors[i].step_size;
-    a.t[i].bc2_sqrt = tensors[i].bc2_sqrt;
-  }
+  AdamArgs a;
+  adam_args(&a, P, G, exp_avg, exp_avg_sq, lr, weight_decay, beta1, beta2, eps, tensors, ntensors, sched);
   HIPCHK(launch_adamw(a, reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;
 }
@@ -1166,25 +1137,10 @@ int pgp_adamw_table_many_d(int n_cells, long long slot_len, const int* active, f
   if (!P || !G || !exp_avg || !exp_avg_sq || !sched || (ntensors > 0 && !tensors))
     return fail(PGP_ERR_ARG, "bad adamw_table_many arguments");
   if (ntensors == 0) return PGP_OK;
-  AdamArgs a{};
-  a.param = P;
-  a.grad = const_cast<float*>(G);
-  a.m = exp_avg;
-  a.v = exp_avg_sq;
-  a.lr_wd = lr * weight_decay;
-  a.b2 = (float)beta2;
-  a.omb1 = adam_moment_weight(beta1);
-  a.omb2 = adam_moment_weight(beta2);
-  a.eps = eps;
-  a.ntensors = ntensors;
-  a.sched = sched;
-  for (int i = 0; i < ntensors; ++i) {
-    if (tensors[i].offset < 0 || tensors[i].n < 0 || tensors[i].offset + tensors[i].n > slot_len)
-      return fail(PGP_ERR_ARG, "AdamW tensor outside the slot");
-    a.t[i].off = (long)tensors[i].offset;
-    a.t[i].n = tensors[i].n;
-    a.t[i].active = kAdamFromTable;  // every row from the cell's table
-  }
+  AdamArgs a;
+  if (!adam_args(&a, P, G, exp_avg, exp_avg_sq, lr, weight_decay, beta1, beta2, eps, tensors, ntensors, sched, 0,
+                 (long)slot_len))
+    return fail(PGP_ERR_ARG, "AdamW tensor outside the slot");
   HIPCHK(launch_adamw_cells(a, n_cells, (long)slot_len, active, (long)sched_cell_stride,
                             reinterpret_cast<hipStream_t>(stream)));
   return PGP_OK;

@@ -19,14 +19,18 @@ constexpr int kAdamChunk = 1024;
 struct AdamGrid {
   int bx0[kMaxTensors + 1];
 };
-__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, AdamGrid g) {
-  const int bx = blockIdx.x;
-  int lo = 0, hi = a.ntensors - 1;  // the last tensor whose first block is <= bx
+// the tensor that owns block bx: the last one whose first block is <= bx
+__device__ __forceinline__ int block_tensor(const AdamGrid& g, int ntensors, int bx) {
+  int lo = 0, hi = ntensors - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
     if (bx >= g.bx0[mid]) lo = mid;
     else hi = mid - 1;
   }
+  return lo;
+}
+__global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a, AdamGrid g) {
+  const int bx = blockIdx.x, lo = block_tensor(g, a.ntensors, bx);
   const AdamTensor& t = a.t[lo];
   float step_size = t.step_size, bc2_sqrt = t.bc2_sqrt;
   if (a.sched && (t.active & kAdamFromTable)) {  // per-step scalars from the device (graph-captured loops)
@@ -54,13 +58,7 @@ __global__ __launch_bounds__(256) void adamw_cells_kernel(AdamArgs a, AdamGrid g
                                                           long slot_len, long sched_stride) {
   const long c = blockIdx.y;
   if (active && !active[c]) return;
-  const int bx = blockIdx.x;
-  int lo = 0, hi = a.ntensors - 1;  // the last tensor whose first block is <= bx
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (bx >= g.bx0[mid]) lo = mid;
-    else hi = mid - 1;
-  }
+  const int bx = blockIdx.x, lo = block_tensor(g, a.ntensors, bx);
   const AdamTensor& t = a.t[lo];
   const float* r = a.sched + c * sched_stride + 3 * lo;
   if (r[0] == 0.f) return;
@@ -78,14 +76,18 @@ __global__ __launch_bounds__(256) void adamw_cells_kernel(AdamArgs a, AdamGrid g
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-hipError_t launch_adamw(const AdamArgs& a, hipStream_t st) {
-  AdamGrid g{};
+static int adam_grid(const AdamArgs& a, AdamGrid* g) {  // fills g->bx0, returns the grid's blocks
   int nb = 0;
   for (int i = 0; i < a.ntensors; ++i) {
-    g.bx0[i] = nb;
+    g->bx0[i] = nb;
     nb += (int)((a.t[i].n + kAdamChunk - 1) / kAdamChunk);
   }
-  g.bx0[a.ntensors] = nb;
+  return g->bx0[a.ntensors] = nb;
+}
+
+hipError_t launch_adamw(const AdamArgs& a, hipStream_t st) {
+  AdamGrid g{};
+  const int nb = adam_grid(a, &g);
   if (nb == 0) return hipSuccess;
   adamw_kernel<<<nb, 256, 0, st>>>(a, g);
   return hipGetLastError();
@@ -95,12 +97,7 @@ hipError_t launch_adamw_cells(const AdamArgs& a, int n_cells, long slot_len, con
                               long sched_cell_stride, hipStream_t st) {
   if (!a.sched || n_cells > 65535) return hipErrorInvalidValue;  // table-driven only; cells on grid y
   AdamGrid g{};
-  int nb = 0;
-  for (int i = 0; i < a.ntensors; ++i) {
-    g.bx0[i] = nb;
-    nb += (int)((a.t[i].n + kAdamChunk - 1) / kAdamChunk);
-  }
-  g.bx0[a.ntensors] = nb;
+  const int nb = adam_grid(a, &g);
   if (nb == 0 || n_cells <= 0) return hipSuccess;
   adamw_cells_kernel<<<dim3(nb, n_cells), 256, 0, st>>>(a, g, active, slot_len, sched_cell_stride);
   return hipGetLastError();

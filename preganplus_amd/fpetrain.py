@@ -25,41 +25,36 @@ cell.  Every model keeps the bits of a lone run."""
 from __future__ import annotations
 
 import ctypes
-import math
 
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, adamw
 from . import weights as W
-from .train import PROTO_FACTOR_DECAY, PROTO_UPDATE_MIN, TuneState, _AdamTensor, accuracy_scores
+from .train import PROTO_FACTOR_DECAY, PROTO_UPDATE_MIN, TuneState, accuracy_scores
 
 FPE_LR = 1e-4          # FPE_16.lr (models.py:14)
 SUPPORTED_H = (16, 50)  # the host counts pgp_fpetrain.hip is compiled for
-COND = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")   # no gradient without a positive label
-
-
-def adam_rows(tensors, positive: bool, lr, b1, b2):
-    """One torch.optim.AdamW.step's per-tensor scalars as Python doubles,
-    [(active, lr / (1 - b1^step), sqrt(1 - b2^step))] in the tensors' order, and
-    the step counts advanced: a tensor of COND takes no step on a window
-    without a positive label (torch skips a parameter without a gradient).
-    The one place this arithmetic lives: ``FPETrainer.adam_step``'s descriptors
-    and ``adam_table``'s rows are these values rounded to fp32."""
-    rows = []
-    for t in tensors:
-        active = positive or t["name"] not in COND
-        if active:
-            t["step"] += 1
-        st = max(t["step"], 1.0)
-        rows.append((int(active), lr / (1 - b1 ** st), math.sqrt(1 - b2 ** st)))
-    return rows
+COND = adamw.COND_TENSORS   # no gradient without a positive label
 
 
 def adam_table(tensors, positive, lr, b1, b2):
-    """``adam_rows`` of consecutive steps, float32 [len(positive), len(tensors), 3]."""
-    rows = [adam_rows(tensors, bool(p), lr, b1, b2) for p in positive]
-    return np.asarray(rows, dtype=np.float64).reshape(len(rows), len(tensors), 3).astype(np.float32)
+    """The AdamW rows of consecutive steps, float32 [len(positive), len(tensors),
+    3] = (active, step_size, bc2_sqrt) (``adamw.schedule``), and the tensors'
+    step counts advanced: a tensor of COND takes no step on a window without a
+    positive label (torch skips a parameter without a gradient)."""
+    table, steps = adamw.schedule([t["step"] for t in tensors], adamw.stepping([t["name"] for t in tensors], positive),
+                                  lr, b1, b2)
+    for t, st in zip(tensors, steps.tolist()):
+        t["step"] = st
+    return table
+
+
+def adam_rows(tensors, positive: bool, lr, b1, b2):
+    """One torch.optim.AdamW.step's per-tensor scalars [(active, step_size,
+    bc2_sqrt)] in the tensors' order — ``adam_table``'s row of that one step,
+    as ``FPETrainer.adam_step`` puts it in its descriptors."""
+    return [(int(a), float(s), float(b)) for a, s, b in adam_table(tensors, [positive], lr, b1, b2)[0]]
 
 
 def fpe_blob(fpe: dict, H: int = 16) -> torch.Tensor:
@@ -114,13 +109,11 @@ class FPETrainer:
     def adam_step(self, positive: bool):
         """torch.optim.AdamW.step (utils.py:65); the prototype decoder had no
         gradient when the window has no positive label (torch skips it)."""
-        arr = [_AdamTensor(t["offset"], t["n"], *r)
-               for t, r in zip(self.tensors, adam_rows(self.tensors, positive, self.lr, self.b1, self.b2))]
-        desc = (_AdamTensor * len(arr))(*arr)
+        desc = adamw.descriptors(self.tensors, adam_rows(self.tensors, positive, self.lr, self.b1, self.b2))
         _native.check(self._L.pgp_adamw_d(
             ctypes.c_void_p(self.P.data_ptr()), ctypes.c_void_p(self.G.data_ptr()),
             ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
-            self.lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw_d")
+            self.lr, self.wd, self.b1, self.b2, self.eps, desc, len(desc), self._stream()), "pgp_adamw_d")
 
     def adam_table(self, positive):
         """The rows n consecutive ``adam_step(positive[i])`` calls put in their
@@ -131,8 +124,7 @@ class FPETrainer:
 
     def _desc(self):
         """The tensors' places in the blob (offset, n): what a table-driven update reads of a descriptor."""
-        return (_AdamTensor * len(self.tensors))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0)
-                                                   for t in self.tensors])
+        return adamw.descriptors(self.tensors)
 
     def backprop(self, st: TuneState, wins, h0s, anom, cls, one_launch=False):
         """train.py:42-57 over the windows: one device step per window (forward,
@@ -258,7 +250,7 @@ class FPEFleetTrainer:
 
     def _desc(self):
         ts = self.tensors[0]
-        return (_AdamTensor * len(ts))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in ts]), len(ts)
+        return adamw.descriptors(ts), len(ts)
 
     # ---------------- one model as a lone FPETrainer, and back ----------------
     def trainer(self, m: int) -> FPETrainer:

@@ -15,7 +15,6 @@ where the ranks' increments are reduced.
 from __future__ import annotations
 
 import ctypes
-import math
 import os
 
 import types
@@ -23,7 +22,7 @@ import types
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, adamw
 from . import weights as W
 from ._native import _COLL_FN, _AdamTensor, _OnlineDesc, _OnlineTensor  # noqa: F401  (the header's structs)
 
@@ -32,6 +31,7 @@ PROTO_UPDATE_MIN = 0.02     # constants.py:14
 PROTO_FACTOR_DECAY = 0.995  # constants.py:15
 LATEST_WINDOW_SIZE = 10     # constants.py:16
 PERCENTILES = 98            # constants.py:11
+COND_TENSORS = adamw.COND_TENSORS   # the prototype decoder: no gradient without a positive label
 
 
 # the current stream's raw handle by device index (torch's C++ accessor; None
@@ -192,8 +192,7 @@ class Trainer:
         key = ("desc",) + tuple((t["offset"], t["n"]) for t in sel)
         c = self._desc_cache.get(key)
         if c is None:
-            c = (_AdamTensor * len(sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in sel])
-            self._desc_cache[key] = c
+            c = self._desc_cache[key] = adamw.descriptors(sel)
         return c
 
     # ---------------- ops ----------------
@@ -374,7 +373,7 @@ class Trainer:
         Disc BCE step + AdamW (device table tabD [len(selD),3]), Gen step through
         the updated Disc + AdamW (tabG), the updated GAN's probabilities.
         target [2] device fp32; probs_gen / probs_after [2] device outputs."""
-        desc = lambda sel: (_AdamTensor * len(sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in sel])
+        desc = adamw.descriptors
         _native.check(self._L.pgp_gan_step1_d(
             self.H, target.data_ptr(), self.P.data_ptr(), self.G.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
             self.lrs["disc"], self.lrs["gen"], self.wd, self.b1, self.b2, self.eps,
@@ -409,59 +408,28 @@ class Trainer:
         """torch.optim.AdamW.step for the tensors of `section` (utils.py:65);
         tensors named in `inactive` had no gradient and are skipped, as torch
         skips params whose .grad is None."""
-        lr = self.lrs[section]
-        arr = []
-        for t in self.tensors:
-            if t["section"] != section or not t["trainable"]:
-                continue
-            active = t["name"] not in inactive
-            if active:
-                t["step"] += 1
-            st = max(t["step"], 1.0)
-            arr.append(_AdamTensor(t["offset"], t["n"], int(active), lr / (1 - self.b1 ** st),
-                                   math.sqrt(1 - self.b2 ** st)))
-        desc = (_AdamTensor * len(arr))(*arr)
+        sel = self.trainable(section)
+        rows = self.adam_schedule_np(section, [False], inactive)[0]
         _native.check(self._L.pgp_adamw_d(
             ctypes.c_void_p(self.P.data_ptr()), ctypes.c_void_p(self.G.data_ptr()),
             ctypes.c_void_p(self.m.data_ptr()), ctypes.c_void_p(self.v.data_ptr()),
-            lr, self.wd, self.b1, self.b2, self.eps, desc, len(arr), self._stream()), "pgp_adamw_d")
-
-    def adam_schedule(self, section: str, inactive_per_step):
-        """adam_step's host bookkeeping for a sequence of steps, done ahead:
-        returns the section's trainable tensors and a [steps, T, 3] fp32 table
-        of (active, step_size, bc2_sqrt) — the values adam_step would pass —
-        and advances the tensors' step counts as those steps would."""
-        lr = self.lrs[section]
-        sel = [t for t in self.tensors if t["section"] == section and t["trainable"]]
-        tab = np.zeros((len(inactive_per_step), len(sel), 3), dtype=np.float32)
-        for s, inactive in enumerate(inactive_per_step):
-            for k, t in enumerate(sel):
-                active = t["name"] not in inactive
-                if active:
-                    t["step"] += 1
-                st = max(t["step"], 1.0)
-                tab[s, k] = (float(active), lr / (1 - self.b1 ** st), math.sqrt(1 - self.b2 ** st))
-        return sel, tab
+            self.lrs[section], self.wd, self.b1, self.b2, self.eps, adamw.descriptors(sel, rows), len(sel),
+            self._stream()), "pgp_adamw_d")
 
     def adam_schedule_np(self, section: str, positive, cond_names):
-        """adam_schedule for the tuning loop's pattern, vectorised: step s of a
-        call skips the tensors named in cond_names unless positive[s] (the
-        prototype decoder gets no gradient from a window without a positive
-        label).  Same values as adam_schedule, same step-count advance."""
-        lr = self.lrs[section]
+        """adam_step's host bookkeeping for a sequence of steps, done ahead: the
+        [steps, T, 3] fp32 table of (active, step_size, bc2_sqrt) over the
+        section's trainable tensors — the values adam_step would pass — with
+        the tensors' step counts advanced as those steps would.  Step s skips
+        the tensors named in cond_names unless positive[s] (the prototype
+        decoder gets no gradient from a window without a positive label).
+        Reads ``tensors``, ``lrs``, ``b1`` and ``b2`` alone, so the host tests
+        call it on a stand-in without a device."""
         sel = [t for t in self.tensors if t["section"] == section and t["trainable"]]
-        positive = np.asarray(positive, dtype=bool)
-        cond = np.array([t["name"] in cond_names for t in sel])
-        active = np.where(cond[None, :], positive[:, None], True)                # [steps, T]
-        step0 = np.array([t["step"] for t in sel], dtype=np.float64)
-        steps = step0[None, :] + np.cumsum(active, axis=0)
-        st = np.maximum(steps, 1.0)
-        tab = np.empty(active.shape + (3,), dtype=np.float32)
-        tab[..., 0] = active
-        tab[..., 1] = lr / (1 - self.b1 ** st)
-        tab[..., 2] = np.sqrt(1 - self.b2 ** st)
-        for k, t in enumerate(sel):
-            t["step"] = float(steps[-1, k])
+        on = adamw.stepping([t["name"] for t in sel], positive, cond_names)
+        tab, steps = adamw.schedule([t["step"] for t in sel], on, self.lrs[section], self.b1, self.b2)
+        for t, st in zip(sel, steps.tolist()):
+            t["step"] = st
         return tab
 
     def adam_step_table(self, section: str, sel, sched):
@@ -699,7 +667,7 @@ class DPTuner:
     them).  ``sync(st)`` copies the state back to a host ``TuneState`` and the
     AdamW step counts back to the Trainer."""
 
-    COND = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")
+    COND = adamw.COND_TENSORS
     CHUNK = 64   # AdamW table rows precomputed per upload
 
     def __init__(self, tr: "Trainer", st: TuneState, max_batch: int, group=None):
@@ -718,7 +686,7 @@ class DPTuner:
         self.inc = torch.zeros(3 * self.K + 3, dtype=torch.float64, device=dev)
         self.ws = torch.zeros(max(int(L.pgp_tune_targets_dp_workspace_len(max_batch)), 1), dtype=torch.float64,
                               device=dev)
-        self.sel = [t for t in tr.tensors if t["section"] == "transformer" and t["trainable"]]
+        self.sel = tr.trainable("transformer")
         self.cond = [k for k, t in enumerate(self.sel) if t["name"] in self.COND]
         self.cond_rows = (ctypes.c_int * len(self.cond))(*self.cond)
         self.cond_steps = torch.tensor([self.sel[k]["step"] for k in self.cond], dtype=torch.float64, device=dev)
@@ -731,12 +699,8 @@ class DPTuner:
         steps for the always-active tensors (their step counts are known ahead);
         the prototype decoder's rows are written per step on the device."""
         tr = self.tr
-        lr = tr.lrs["transformer"]
-        tab = np.zeros((self.CHUNK, len(self.sel), 3), dtype=np.float32)
-        for i in range(self.CHUNK):
-            for k, b in enumerate(self.base):
-                stp = max(b + self.n + i + 1, 1.0)
-                tab[i, k] = (1.0, lr / (1 - tr.b1 ** stp), math.sqrt(1 - tr.b2 ** stp))
+        tab, _ = adamw.schedule(np.array(self.base) + self.n, np.ones((self.CHUNK, len(self.sel)), dtype=bool),
+                                tr.lrs["transformer"], tr.b1, tr.b2)
         self.table.copy_(torch.from_numpy(tab).pin_memory(), non_blocking=True)
 
     SUBSTAGES = ("forward", "targets", "backward", "all_reduce", "apply_adamw")
@@ -1052,7 +1016,7 @@ def backprop(tr: Trainer, st: TuneState, wins, anom, cls, fused: bool | None = N
 
     Every step stays on the device: custom_loss's sequential bookkeeping runs
     in a kernel (state in fp64), AdamW's per-step scalars come from a table
-    computed ahead on the host (``Trainer.adam_schedule``), and the n steps
+    computed ahead on the host (``Trainer.adam_schedule_np``), and the n steps
     replay as one captured HIP graph (``_TuneGraph``, cached per shape).  The
     host uploads the inputs and reads back the results once per call.
     ``loss_targets`` is the same bookkeeping in numpy (the tests restate with
@@ -1088,7 +1052,7 @@ def backprop(tr: Trainer, st: TuneState, wins, anom, cls, fused: bool | None = N
         tr._graphs[key] = g
     positive = np.any(anom > 0, axis=1)
     drop_base = tr.dropout_base()   # before adam_schedule_np advances the counts: masks never repeat across calls
-    tab = tr.adam_schedule_np("transformer", positive, ("prototype_decoder.0.weight", "prototype_decoder.0.bias"))
+    tab = tr.adam_schedule_np("transformer", positive, COND_TENSORS)
     g.launch(tr, wins, anom, cls, st.vector(), tab, stream, drop_base)
 
     def finish():
@@ -1382,7 +1346,7 @@ class SectionRows:
 
     def __init__(self, tr: Trainer, section: str):
         self.tr, self.section = tr, section
-        self.sel = [t for t in tr.tensors if t["section"] == section and t["trainable"]]
+        self.sel = tr.trainable(section)
         self.table = torch.zeros((self.CHUNK, len(self.sel), 3), dtype=torch.float32, device=tr.device)
         self.i = 0
 
@@ -1392,9 +1356,9 @@ class SectionRows:
     def next_row(self, out: torch.Tensor | None = None):
         """The next step's row: a view of the table, or copied into ``out``."""
         if self.i % self.CHUNK == 0:
-            tab = self.tr.adam_schedule_np(self.section, np.ones(self.CHUNK, dtype=bool), ())
-            for t in self.sel:            # adam_schedule_np advanced the counts by CHUNK; one step at a time here
-                t["step"] -= self.CHUNK
+            tr = self.tr                  # the next CHUNK rows; the counts advance one step per call, below
+            tab, _ = adamw.schedule([t["step"] for t in self.sel], np.ones((self.CHUNK, len(self.sel)), dtype=bool),
+                                    tr.lrs[self.section], tr.b1, tr.b2)
             self.table.copy_(torch.from_numpy(tab).pin_memory(), non_blocking=True)
         row = self.table[self.i % self.CHUNK]
         self.i += 1
@@ -1706,7 +1670,6 @@ class OnlineTrainStep:
 # A fleet of cells, each tuned on its own weights (PreGANPlus.py:51-58: every
 # PreGANPlusRecovery owns its Transformer_16; train.py:42-57, 94-109)
 # ---------------------------------------------------------------------------
-COND_TENSORS = ("prototype_decoder.0.weight", "prototype_decoder.0.bias")   # no gradient without a positive label
 bind_fleet = _native.bind   # the earlier helper's name: the previous release's tests reach the library through it
 
 
@@ -1736,7 +1699,7 @@ class FleetSchedule:
         self.sel_disc = [i for i, t in enumerate(self.tensors) if t["section"] == "disc" and t["trainable"]]
         self.sel_gen = [i for i, t in enumerate(self.tensors) if t["section"] == "gen" and t["trainable"]]
         self.sel = [i for i, t in enumerate(self.tensors) if t["section"] == "transformer" and t["trainable"]]
-        self.cond = np.array([self.tensors[i]["name"] in COND_TENSORS for i in self.sel])
+        self.names = [self.tensors[i]["name"] for i in self.sel]
         self.base_col = next(i for i, t in enumerate(self.tensors)
                              if t["section"] == "transformer" and t["name"] == "time_encoder.weight")
         self.steps = np.zeros((self.M, len(self.tensors)), dtype=np.float64)
@@ -1751,20 +1714,13 @@ class FleetSchedule:
         the transformer's trainable tensors; advances the active cells' counts
         as those n steps do.  An inactive cell's rows are zero, its counts stay."""
         positive = np.asarray(positive, dtype=bool)
-        M, n = positive.shape
+        M, _ = positive.shape
         if M != self.M:
             raise ValueError(f"positive: {M} cells, the fleet has {self.M}")
         act = np.ones(M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(M)
-        on = np.where(self.cond[None, None, :], positive[:, :, None], True) & act[:, None, None]   # [M,n,T]
-        steps = self.steps[:, self.sel][:, None, :] + np.cumsum(on, axis=1)
-        st = np.maximum(steps, 1.0)
-        tab = np.empty(on.shape + (3,), dtype=np.float32)
-        tab[..., 0] = on
-        tab[..., 1] = self.lr / (1 - self.b1 ** st)
-        tab[..., 2] = np.sqrt(1 - self.b2 ** st)
+        on = adamw.stepping(self.names, positive) & act[:, None, None]                         # [M,n,T]
+        tab, self.steps[:, self.sel] = adamw.schedule(self.steps[:, self.sel], on, self.lr, self.b1, self.b2)
         tab[~act] = 0.0
-        if n:
-            self.steps[:, self.sel] = steps[:, -1, :]
         return tab
 
     def gan_tables(self, active=None):
@@ -1777,15 +1733,10 @@ class FleetSchedule:
         act = np.ones(self.M, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(self.M)
         out = []
         for sel, lr in ((self.sel_disc, self.lrs["disc"]), (self.sel_gen, self.lrs["gen"])):
-            steps = self.steps[:, sel] + act[:, None]
-            st = np.maximum(steps, 1.0)
-            tab = np.empty(steps.shape + (3,), dtype=np.float32)
-            tab[..., 0] = 1.0
-            tab[..., 1] = lr / (1 - self.b1 ** st)
-            tab[..., 2] = np.sqrt(1 - self.b2 ** st)
+            on = np.broadcast_to(act[:, None, None], (self.M, 1, len(sel)))
+            tab, self.steps[:, sel] = adamw.schedule(self.steps[:, sel], on, lr, self.b1, self.b2)
             tab[~act] = 0.0
-            self.steps[:, sel] = steps
-            out.append(tab)
+            out.append(tab[:, 0])
         return out[0], out[1]
 
 
@@ -2075,15 +2026,14 @@ class FleetTuner:
         self.state_dev = self.state0           # the device tensor [M,2K+3] that holds the fleet's current state
         self.logits = torch.zeros((M, self.H, 2), dtype=torch.float32, device=dev)
         self.protos = torch.zeros((M, self.H, 2), dtype=torch.float32, device=dev)
-        self._desc = (_AdamTensor * len(self.sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in self.sel])
+        self._desc = adamw.descriptors(self.sel)
         self._graphs = {}
         self._detect_io = None
         self.tune_errors = {}       # cell -> the ZeroDivisionError its last scored tune() met (results)
         # the per-cell GAN step (train_gan): the Disc's / Gen's trainable tensors, offsets relative to the slot
         self.selD = [self.tensors[i] for i in self.sched.sel_disc]
         self.selG = [self.tensors[i] for i in self.sched.sel_gen]
-        desc = lambda sel: (_AdamTensor * len(sel))(*[_AdamTensor(t["offset"], t["n"], 1, 0.0, 0.0) for t in sel])
-        self._descD, self._descG = desc(self.selD), desc(self.selG)
+        self._descD, self._descG = adamw.descriptors(self.selD), adamw.descriptors(self.selG)
         self._gan_graphs = {}
         self.gan_capture = True     # False: train_gan issues its launches eagerly (the tests hold both equal)
         self.gan_probs_after = np.zeros((M, 2), dtype=np.float32)

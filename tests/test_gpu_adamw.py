@@ -78,7 +78,7 @@ def down(dev):
 
 
 def rows(tensors, hy):
-    """The device table rows (active, step_size, bc2_sqrt) of a tensor list, as Trainer.adam_schedule writes them."""
+    """The device table rows (active, step_size, bc2_sqrt) of a tensor list, as Trainer.adam_schedule_np writes them."""
     return np.array([[float(a), hy["lr"] / (1 - hy["b1"] ** max(s, 1)), np.sqrt(1 - hy["b2"] ** max(s, 1))]
                      for _, _, a, s in tensors], dtype=np.float32)
 
@@ -212,6 +212,44 @@ def test_table_many_cells():
     after = down(dev)
     for k in host:
         assert np.array_equal(AR.bits(after[k]), AR.bits(host[k])), k
+
+
+def test_three_entries_agree_across_the_block_edge():
+    """pgp_adamw_d, pgp_adamw_table_d and pgp_adamw_table_many_d leave identical bits on one tensor list whose
+    lengths straddle the 1024-element block (1, 1023, 1025, 2048: the smallest at which a wrong block -> tensor
+    lookup or a wrong slot offset shows), one step; the fleet entry with a second, inactive cell that keeps its
+    bits.  The step itself is held to the replay's bound."""
+    L = _native.lib()
+    hy = AR.HYPERS["project"]
+    lay, slot_len = layout((1, 1023, 1025, 2048))
+    tensors = [(o, n, 1, 3) for o, n in lay]
+    T = len(tensors)
+    cells = []
+    for seed in (61, 62):
+        h = dict(zip("PmvG", AR.synthetic(slot_len, seed, fresh=False)))
+        gap = ~AR.active_mask(slot_len, tensors)
+        for a in h.values():
+            a[gap] = SENTINEL
+        cells.append(h)
+    out = {}
+    for entry in ("pgp_adamw", "pgp_adamw_table"):
+        dev = up(cells[0])
+        run_entry(entry, dev, tensors, hy)
+        out[entry] = down(dev)
+    record("block edge", AR.assert_step("pgp_adamw, block edge", cells[0], out["pgp_adamw"], tensors, **hy))
+    host = {k: np.concatenate([c[k] for c in cells]) for k in "PmvG"}
+    dev = up(host)
+    active = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
+    sched = torch.from_numpy(np.stack([rows(tensors, hy)] * 2)).cuda()     # cell 1's rows say active: its flag rules
+    desc = (TR._AdamTensor * T)(*[TR._AdamTensor(o, n, 1, 7.0, 0.5) for o, n in lay])
+    _native.check(L.pgp_adamw_table_many_d(2, slot_len, active.data_ptr(), *(dev[k].data_ptr() for k in "PGmv"),
+                                           *hyper_args(hy), desc, T, sched.data_ptr(), 3 * T, None),
+                  "pgp_adamw_table_many")
+    many = down(dev)
+    for k in "PmvG":
+        assert np.array_equal(AR.bits(out["pgp_adamw_table"][k]), AR.bits(out["pgp_adamw"][k])), k
+        assert np.array_equal(AR.bits(many[k][:slot_len]), AR.bits(out["pgp_adamw"][k])), k
+        assert np.array_equal(AR.bits(many[k][slot_len:]), AR.bits(cells[1][k])), k
 
 
 @pytest.mark.parametrize("entry", ["pgp_adamw", "pgp_adamw_table", "pgp_adamw_table_many"])

@@ -18,7 +18,6 @@ count.  There is no CPU path: without a GPU the tool fails.
 import argparse
 import ctypes
 import json
-import math
 import os
 import sys
 
@@ -27,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from preganplus_amd import _native  # noqa: E402
+from preganplus_amd import _native, adamw  # noqa: E402
 from preganplus_amd import fpetrain as FT  # noqa: E402
 from preganplus_amd import train as TR  # noqa: E402
 from preganplus_amd import weights as W  # noqa: E402
@@ -64,10 +63,8 @@ def measure(H, steps, windows, reps):
     state = torch.tensor(TR.TuneState(w["prototypes"], 0.2).vector(), dtype=torch.float64, device="cuda")
     loss = torch.zeros(2, dtype=torch.float64, device="cuda")
     # AdamW descriptors of a mid-training step (the bias corrections are host scalars)
-    st = 100.0
-    arr = [FT._AdamTensor(t["offset"], t["n"], 1, ft.lr / (1 - ft.b1 ** st), math.sqrt(1 - ft.b2 ** st))
-           for t in ft.tensors]
-    desc = (FT._AdamTensor * len(arr))(*arr)
+    rows = FT.adam_rows([dict(t, step=99.0) for t in ft.tensors], True, ft.lr, ft.b1, ft.b2)
+    desc = adamw.descriptors(ft.tensors, rows)
     stream = ft._stream()
     P, G, m, v = (vp(t.data_ptr()) for t in (ft.P, ft.G, ft.m, ft.v))
 
@@ -75,7 +72,7 @@ def measure(H, steps, windows, reps):
         for _ in range(steps):
             rc = L.pgp_fpe_train_step(H, 3, win.data_ptr(), h0.data_ptr(), y.data_ptr(), c.data_ptr(), P, G,
                                       state.data_ptr(), TR.PROTO_UPDATE_MIN, 1.0, loss.data_ptr(), stream)
-            rc |= L.pgp_adamw_d(P, G, m, v, ft.lr, ft.wd, ft.b1, ft.b2, ft.eps, desc, len(arr), stream)
+            rc |= L.pgp_adamw_d(P, G, m, v, ft.lr, ft.wd, ft.b1, ft.b2, ft.eps, desc, len(desc), stream)
             if rc:
                 _native.check(rc, "step")
 
